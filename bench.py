@@ -2,12 +2,16 @@
 """bench.py -- the hot path's headline metric on MI355X: Qwen2-VL-2B INT4 (Q4_K) decode tok/s + 448x448 image prefill ms.
 
     python bench.py --gpus 1 --steps 256 --warmup 16                 # headline (BASELINE.json configs[3])
+    python bench.py --full                                           # + vision prefill batch, rooflines, per-kernel timings, batched decode, CPU baseline
+    python bench.py --dump-outputs DIR                               # + DIR/tokens.npy: the ids the timed steps produced (config vit: DIR/vision.npy)
     python bench.py --config qwen15|tinyllama|llava|vit              # the other BASELINE configs on the same resident engine
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one greedy decode forward (one token) after the config's synthetic prompt prefill (qwen2vl: 448x448 image + 24 tokens, S = 282).
 Timed exactly like Module::profiling() (mllm/Module.cpp:35-42): TTFT = the prefill forward (median of 5 here), decode tok/s = steps / time of
 the following forwards -- the K forwards run back to back on the device (argmax on device), bracketed by barrier + synchronize, max over ranks.
+Exactly K steps are timed: steps that do not fit in the config's KV slab behind the prompt and the warmup run in further segments, each after an
+untimed prefill of the same prompt.  A plain run times the headline only; --full adds the extras below, each measured after the timed steps.
 N > 1: the LLM path does not shard ("replicas only"): every rank decodes its own replica (weak scaling, value = N*K/t).  The vision prefill does
 shard: a batch of images is split over the ranks, each rank runs the tower on its images and one RCCL all-gather reassembles the visual-token
 sequence (reported as vit_prefill, not part of `value`).  config vit has no decode: a step is one image through the tower (value = images/s).
@@ -34,6 +38,20 @@ WORKLOADS = {
     "llava": "demo_llava LLaVA-1.5-7B Q4_K + CLIP-ViT-L/14-336: one 336x336 image + 13 text tokens (S=589), then greedy decode, KV limit 700",
     "vit": "demo_vit ViT-B/16 224x224 Q4_K: image batch through patch embedding + 12 encoder blocks + classifier",
 }
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy, float32 kept, anything else as float64 (token ids are exact in it).  At most DUMP_BYTES in all: an array
+    over its share is replaced by a fixed, seeded sample of its flattened elements, so that two runs with the same arguments write comparable files."""
+    os.makedirs(d, exist_ok=True)
+    share = (DUMP_BYTES - 4096) // len(arrays)      # (less the .npy headers)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline(path, rank, ids, pix):
@@ -186,18 +204,21 @@ def dry_run(args):
         return float(t.item())
 
     eng = StubEngine(rank)
-    nb = max(args.vit_batch, world)
-    batch = torch.arange(nb * 4 * 3, dtype=torch.float32).reshape(nb, 4, 3)
+    vit = None
+    if args.full:
+        nb = max(args.vit_batch, world)
+        batch = torch.arange(nb * 4 * 3, dtype=torch.float32).reshape(nb, 4, 3)
 
-    def run_vision(px):
-        eng.vision(px.shape[0])
-        return px * 2.0
-    barrier()
-    t0 = time.perf_counter()
-    full = parallel.sharded_vision(run_vision, batch, pass_images=1)
-    barrier()
-    dtv = rmax(time.perf_counter() - t0)
-    assert torch.equal(full, batch * 2.0)
+        def run_vision(px):
+            eng.vision(px.shape[0])
+            return px * 2.0
+        barrier()
+        t0 = time.perf_counter()
+        full = parallel.sharded_vision(run_vision, batch, pass_images=1)
+        barrier()
+        dtv = rmax(time.perf_counter() - t0)
+        assert torch.equal(full, batch * 2.0)
+        vit = {"images": nb, "ms": round(dtv * 1e3, 3), "world": world, "all_gathers": len(parallel.pass_groups((nb + world - 1) // world, 1))}
     prefill_ms = rmax(eng.prefill())
     K, W = args.steps, args.warmup
     eng.generate(W)
@@ -209,9 +230,8 @@ def dry_run(args):
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": round(world * K / dt, 2), "unit": "tok/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt * 1e3 / K, 4),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "none", "data": "none (dry run: stub engine on gloo, plumbing check only)",
-                          "dry_run": True, "config": {"workload": "stub", "parallelism": "replicas" if world > 1 else "single", "rccl_world": world},
-                          "prefill_ms": round(prefill_ms, 3), "roofline": None, "cpu_baseline": None,
-                          "vit_prefill": {"images": nb, "ms": round(dtv * 1e3, 3), "world": world, "all_gathers": len(parallel.pass_groups((nb + world - 1) // world, 1))}}))
+                          "dry_run": True, "full": args.full, "config": {"workload": "stub", "parallelism": "replicas" if world > 1 else "single", "rccl_world": world},
+                          "prefill_ms": round(prefill_ms, 3), "roofline": None, "cpu_baseline": None, "vit_prefill": vit}))
     if world > 1:
         dist.destroy_process_group()
 
@@ -222,11 +242,16 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--config", default="qwen2vl", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--vit-batch", type=int, default=8)
-    ap.add_argument("--no-batched", dest="batched", action="store_false", help="skip the batched-decode extra (B = 2, 4, 8 sequences per step)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the extras: the sharded vision prefill (vit_prefill), roofline with per-kernel "
+                                                         "and per-launch timings, prefill_roofline, batched_decode and cpu_baseline (a plain run leaves them null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed steps computed to DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--vit-batch", type=int, default=8, help="images of the vit_prefill extra (--full); config vit: 8 x this many images per timed batch")
+    ap.add_argument("--no-batched", dest="batched", action="store_false", help="--full without the batched-decode extra (B = 2, 4, 8, 15 sequences per step)")
     ap.add_argument("--dry-run", action="store_true", help="plumbing check without a GPU: gloo + a stub engine with fixed per-rank step times; the line says dry_run and is no measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dry_run:
         return dry_run(args)
 
@@ -282,7 +307,16 @@ def main():
     t_load = time.time() - t0
     load = m.load_stats()
 
-    # ---- sharded vision prefill (N > 1: image batch split over ranks + one all-gather); config vit: this IS the step -------------------------
+    def finish(line, outputs):
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
+            print(json.dumps(line))
+        m.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    # ---- sharded vision prefill (N > 1: image batch split over ranks + one all-gather), an extra of --full; config vit: this IS the step -----
     def tower_batch(nb):
         if cfgname == "qwen2vl":
             return torch.from_numpy(np.stack([np.roll(image, i, axis=0) for i in range(nb)]))          # [nb, 1024, 1176] host pixels
@@ -292,7 +326,7 @@ def main():
 
     vit = None
     has_tower = cfgname in ("qwen2vl", "llava", "vit")
-    if has_tower and (args.vit_batch > 0 or cfgname == "vit"):
+    if cfgname == "vit" or (args.full and has_tower and args.vit_batch > 0):
         nb = max(args.vit_batch, world) if cfgname != "vit" else max(args.vit_batch, 1) * 8
         rows, cols = m.vision_shape(meta)
         batch = tower_batch(nb)
@@ -305,32 +339,31 @@ def main():
         tower_tokens = {"qwen2vl": int(batch.shape[1]), "llava": rows + 1, "vit": 197}[cfgname]
         vis_pass = max(1, min(32, 6400 // tower_tokens))      # images per tower pass: the engine's own pass size (about 6400 token rows)
         run_vision(batch[:1])  # warm
-        reps = max(1, args.steps // nb) if cfgname == "vit" else 1
+        sizes = [nb]
+        if cfgname == "vit":      # exactly K images, nb per batch, the last batch short
+            sizes = [nb] * (args.steps // nb) + ([args.steps % nb] if args.steps % nb else [])
         barrier()
         t0 = time.perf_counter()
-        for _ in range(reps):
+        for n in sizes:
             # image shard per rank; with more than one rank the all-gather of tower pass g (RCCL over xGMI) travels while pass g + 1 is computed
-            full = parallel.sharded_vision(run_vision, batch, pass_images=vis_pass if world > 1 else 0)
+            full = parallel.sharded_vision(run_vision, batch[:n], pass_images=vis_pass if world > 1 else 0)
         barrier()
-        dtv = rmax(time.perf_counter() - t0) / reps
-        assert tuple(full.shape) == (nb, rows, cols)
+        dtv = rmax(time.perf_counter() - t0) * nb / sum(sizes)      # per batch of nb images
+        assert tuple(full.shape) == (sizes[-1], rows, cols)
         flops = {"qwen2vl": 1.48e12, "llava": 0.39e12, "vit": 35e9}[cfgname]      # SURVEY §8(d) algorithmic FLOPs per image
         vit = {"images": nb, "ms": round(dtv * 1e3, 3), "images_per_s": round(nb / dtv, 2), "tflops": round(flops * nb / dtv / 1e12, 2),
                "frac_of_bf16_mfma_peak_2500TF": round(flops * nb / dtv / 2.5e15, 4), "checksum": round(float(full.double().sum().item()), 3),
                "world": world, "note": "tower incl. H2D of the pixels; a rank walks its images several per pass (about 6400 token rows), the upload of pass g+1 overlaps the tower on pass g; image batch sharded over ranks, 1 all-gather"}
 
     if cfgname == "vit":
-        if rank == 0:
-            print(json.dumps({
-                "metric": METRIC, "value": vit["images_per_s"], "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(vit["ms"] / vit["images"], 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-                "dtype": "int8xint4->int32, fp32 accumulate (Q8_K x Q4_K)", "data": "synthetic", "config": {"workload": WORKLOADS[cfgname], "parallelism": f"image shard x{world}"},
-                "roofline": {"bound": "mfma", "achieved": vit["tflops"], "peak": 2500.0, "unit": "TFLOP/s", "frac": vit["frac_of_bf16_mfma_peak_2500TF"], "traffic": None},
-                "cpu_baseline": None, "vit_prefill": vit, "setup_s": {"weights": round(t_weights, 1), "load": round(t_load, 2)}, "load": load}))
-        m.close()
-        if world > 1:
-            dist.destroy_process_group()
-        return
+        return finish({
+            "metric": METRIC, "value": vit["images_per_s"], "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(vit["ms"] / vit["images"], 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "int8xint4->int32, fp32 accumulate (Q8_K x Q4_K)", "data": "synthetic", "full": args.full,
+            "config": {"workload": WORKLOADS[cfgname], "parallelism": f"image shard x{world}"},
+            "roofline": {"bound": "mfma", "achieved": vit["tflops"], "peak": 2500.0, "unit": "TFLOP/s", "frac": vit["frac_of_bf16_mfma_peak_2500TF"], "traffic": None},
+            "cpu_baseline": None, "vit_prefill": vit, "setup_s": {"weights": round(t_weights, 1), "load": round(t_load, 2)}, "load": load},
+            {"vision": full.cpu().numpy()})      # the last timed batch's classifier outputs
 
     # ---- prefill: one warm run (first touch, code load), then the median of 5 timed runs (TTFT; inputs resident in HBM when the clock starts) ----
     m.prefill(ids, image, meta, want_logits=False)
@@ -343,25 +376,51 @@ def main():
     prefill_ms = rmax(float(np.median(pre)))
     S = int(ids.size) if cfgname != "llava" else int(ids.size) - 1 + cfg.v_tokens
 
-    # ---- decode: W warmup steps, then exactly K timed steps ----------------------------------------------------------
+    # ---- decode: W warmup steps, then exactly K timed steps.  Steps past the end of the KV slab run in further segments, each after an untimed prefill of the same
+    # prompt, so their contexts span S .. cache_limit again; the clock runs only around the segments' steps ---------------------------------------------------------
     K, W = args.steps, args.warmup
-    if cfgname == "llava" and S + K + W + 1 > cfg.cache_limit:
-        K = max(8, cfg.cache_limit - S - W - 1 - 4)      # (four slots stay free for the launch-by-launch steps of roofline.step_launches)
-    assert S + K + W + 1 <= cfg.cache_limit, "steps + warmup exceed the KV slab of the config"
+    spare = 8 if args.full else 0      # (slots left free for the launch-by-launch steps of roofline.step_launches)
+    room = lambda start: cfg.cache_limit - start - 1 - spare
+    if room(S + W) < 1:
+        raise SystemExit(f"--warmup {W} leaves no room for a timed step in the KV slab of config {cfgname} ({cfg.cache_limit} tokens, prompt {S})")
     if W > 0:
         toks, _ = m.generate(tok, W)
         tok = int(toks[-1])
-    barrier()
-    t0 = time.perf_counter()
-    toks, dev_ms = m.generate(tok, K)
-    barrier()
-    dt = rmax(time.perf_counter() - t0)
+    segs, outs, done, dt, dev_ms, start = [], [], 0, 0.0, 0.0, S + W
+    while done < K:
+        if done:
+            m.clear_kvcache()
+            tok, _, _ = m.prefill(ids, image, meta, want_logits=False)
+            start = S
+        n = min(K - done, room(start))
+        barrier()
+        t0 = time.perf_counter()
+        toks, ms = m.generate(tok, n)
+        barrier()
+        dt += time.perf_counter() - t0
+        dev_ms += ms
+        segs.append((start, n))
+        outs.append(toks)
+        tok, done = int(toks[-1]), done + n
+    toks = np.concatenate(outs)
+    dt = rmax(dt)
     value = world * K / dt
+    line = {
+        "metric": METRIC, "value": round(value, 2), "unit": "tok/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt * 1e3 / K, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int8xint4->int32, fp32 accumulate (Q8_K x Q4_K)", "data": "synthetic", "full": args.full,
+        "config": {"workload": WORKLOADS[cfgname], "prefill_tokens": S, "parallelism": "replicas" if world > 1 else "single", "rccl_world": world, "kv_segments": len(segs)},
+        "prefill_ms": round(prefill_ms, 3), "prefill_ms_runs": [round(v, 3) for v in pre], "prefill_tok_s": round(1000.0 * S / prefill_ms, 1),
+        "roofline": None, "prefill_roofline": None, "cpu_baseline": None, "vit_prefill": vit, "batched_decode": None,
+        "setup_s": {"weights": round(t_weights, 1), "load": round(t_load, 2)}, "load": load,
+    }
+    if not args.full:
+        return finish(line, {"tokens": toks})
 
     # ---- roofline (decode is HBM-bound): the whole token first -- algorithmic bytes (weights + KV read) / device time of the K steps -- then
     # the two kernels that matter, each from live HIP events on the engine's stream over 280 launches cycling over the layers (cold HBM like the real step)
     wbytes = m.decode_weight_bytes()
-    T_mid = S + W + K // 2
+    T_mid = sum(n * (c0 + n // 2) for c0, n in segs) // K      # mean context of the timed steps (one segment: S + W + K // 2)
     kv_bytes = cfg.layers * 2 * T_mid * cfg.kv_heads * cfg.head_dim * 2 if cfgname != "llava" else cfg.layers * 2 * T_mid * cfg.heads * cfg.head_dim * 2
     tok_bytes = wbytes + kv_bytes
     tok_gbs = tok_bytes * (K / (dev_ms * 1e-3)) / 1e9
@@ -377,7 +436,7 @@ def main():
     # ---- the step launch by launch: a few more greedy steps run eagerly with a HIP event either side of every launch (mllm_hip_model_time_step).  Since round 4 most of
     # the token is ONE kind of launch -- a layer's down projection + the next layer's q|k|v + attention + o-projection handing their rows over in flight -- which cannot
     # be timed alone (its roles poll each other); this is its live figure, to be read beside the kernel trace's duration of the same kernel in the captured graph
-    step_launches, room = [], cfg.cache_limit - (S + W + K) - 1
+    step_launches, room = [], cfg.cache_limit - sum(segs[-1]) - 1
     if rank == 0 and min(8, room) >= 2:
         b = {k: m.time_kernel(w, 1)[1] for k, w in (("qkv", 10), ("kv", 11), ("o_proj", 12), ("gateup", 13), ("down", 14))}
         b["attn"] = b["kv"]
@@ -463,21 +522,8 @@ def main():
     base = None
     if cfgname == "qwen2vl" and not args.no_cpu_baseline and world == 1:
         base = cpu_baseline(path, rank, ids, image)
-    if rank == 0:
-        out = {
-            "metric": METRIC, "value": round(value, 2), "unit": "tok/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt * 1e3 / K, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "int8xint4->int32, fp32 accumulate (Q8_K x Q4_K)", "data": "synthetic",
-            "config": {"workload": WORKLOADS[cfgname], "prefill_tokens": S, "parallelism": "replicas" if world > 1 else "single", "rccl_world": world},
-            "prefill_ms": round(prefill_ms, 3), "prefill_ms_runs": [round(v, 3) for v in pre], "prefill_tok_s": round(1000.0 * S / prefill_ms, 1),
-            "decode_weight_bytes_per_token": int(wbytes), "roofline": roofline, "prefill_roofline": prefill_roofline, "cpu_baseline": base, "vit_prefill": vit,
-            "batched_decode": batched,
-            "setup_s": {"weights": round(t_weights, 1), "load": round(t_load, 2)}, "load": load,
-        }
-        print(json.dumps(out))
-    m.close()
-    if world > 1:
-        dist.destroy_process_group()
+    line.update({"decode_weight_bytes_per_token": int(wbytes), "roofline": roofline, "prefill_roofline": prefill_roofline, "cpu_baseline": base, "batched_decode": batched})
+    finish(line, {"tokens": toks})
 
 
 if __name__ == "__main__":

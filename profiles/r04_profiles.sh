@@ -8,9 +8,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04
 rm -rf $O && mkdir -p $O
 cd /tmp
-CMD="python3 $R/bench.py --steps 64 --warmup 8 --no-cpu-baseline --vit-batch 2 --no-batched"
+CMD="python3 $R/bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --vit-batch 2 --no-batched"
 rm -rf /tmp/p1 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- $CMD > $O/bench_under_rocprof.log 2>&1
-python3 $R/profiles/summarize.py /tmp/p1 $O/r04_bench_kernel_stats.md "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --vit-batch 2 --no-batched"
+python3 $R/profiles/summarize.py /tmp/p1 $O/r04_bench_kernel_stats.md "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --vit-batch 2 --no-batched"
 cp $(ls /tmp/p1/*/*kernel_stats.csv | head -1) $O/r04_bench_kernel_stats.csv
 echo "stats done"
 rm -rf /tmp/p2 && rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/p2 -- python3 $R/profiles/pmc_decode.py > $O/pmc_fetch.log 2>&1
@@ -43,5 +43,5 @@ print(open(f"{R}/gpurun_out/r04/r04_pmc_sq.md").read())
 PY
 echo "sq done"
 cp $O/r04_pmc_traffic.json $O/r04_pmc_mfma.json $R/profiles/ 2>/dev/null || true
-cd $R && python3 bench.py > $O/r04_bench_line.json 2> $O/bench.err
+cd $R && python3 bench.py --full > $O/r04_bench_line.json 2> $O/bench.err
 echo "bench done"; tail -c 700 $O/r04_bench_line.json

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -121,7 +123,8 @@ def test_bench_fails_loudly_without_a_hip_device():
 def test_bench_two_ranks_dry_run_under_torchrun(tmp_path):
     """bench.py's N > 1 skeleton, launched the way the driver launches it (python -m torch.distributed.run, rendezvous on 127.0.0.1), on gloo with the stub engine of
     --dry-run: rank 1 is 1.25x slower than rank 0 by construction, so the barriers + MAX over ranks must give value = world * K / (K * 1.25 ms) = 1600 tok/s (sleep
-    granularity allows a few per cent), one JSON line from rank 0 only, rccl_world = n_gpus = 2, the vision prefill sharded with one all-gather per tower pass."""
+    granularity allows a few per cent), one JSON line from rank 0 only, rccl_world = n_gpus = 2, the vision prefill (an extra of --full) sharded with one all-gather per
+    tower pass."""
     import json
     import socket
     import subprocess
@@ -129,7 +132,7 @@ def test_bench_two_ranks_dry_run_under_torchrun(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                          os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "4", "--dry-run"], capture_output=True, text=True, timeout=300, cwd=root)
+                          os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "4", "--dry-run", "--full"], capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -143,3 +146,47 @@ def test_bench_two_ranks_dry_run_under_torchrun(tmp_path):
     if not __import__("torch").cuda.is_available():
         bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "0"], capture_output=True, text=True, timeout=300, cwd=root)
         assert bad.returncode != 0 and "no HIP device" in (bad.stderr + bad.stdout)
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays stay float32, ids become float64, and an output over the budget is replaced by the same seeded sample from run to run."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    big, ids = np.arange(1 << 20, dtype=np.float32), np.arange(10, dtype=np.int32)      # 4 MB: over the (patched) 1 MB budget
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "ids": ids})
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "ids.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 1 << 20
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size > 100_000 and np.array_equal(a, b) and np.all(np.diff(a) > 0)      # one fixed sample, in order
+    i = np.load(tmp_path / "a" / "ids.npy")
+    assert i.dtype == np.float64 and np.array_equal(i, ids)
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_exactly_the_steps_asked_for_and_dumps_their_ids(tmp_path):
+    """A plain run (no --full) times exactly --steps greedy steps, also past the end of the KV slab (800 tokens: 282 of prompt + 2 of warmup leave room for 515, the
+    other 85 run after an untimed prefill of the same prompt), leaves the extras null, and --dump-outputs writes the ids those steps produced: the reference's greedy
+    ids of the same prompt on the same file (tests/golden/qwen2vl_2b_ref.npz: the prefill's id, then 64 steps) from step W + 1 on, and from step 1 on in the second segment."""
+    import numpy as np
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "600", "--warmup", "2", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 600 and r["warmup"] == 2 and r["full"] is False and r["config"]["kv_segments"] == 2
+    assert abs(r["value"] - 1000.0 / r["ms_per_step"]) / r["value"] < 1e-3 and r["prefill_ms"] > 0
+    for k in ("roofline", "prefill_roofline", "cpu_baseline", "vit_prefill", "batched_decode"):
+        assert r[k] is None, k
+    assert sorted(os.listdir(d)) == ["tokens.npy"]
+    t = np.load(d / "tokens.npy")
+    assert t.dtype == np.float64 and t.shape == (600,)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "qwen2vl_2b_ref.npz"))["tokens"]
+    room = 800 - 282 - 2 - 1
+    assert np.array_equal(t[:62], g[3:]) and np.array_equal(t[room:room + 64], g[1:])
