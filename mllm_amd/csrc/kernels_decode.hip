@@ -1368,7 +1368,7 @@ __global__ __launch_bounds__(256) void dec_head_kernel(const float *__restrict__
     __syncthreads();
     ss = red[0] + red[1] + red[2] + red[3];
     const float inv = 1.0f / sqrtf((float)(ss / (double)K) + eps);
-    // Q8_0 (quantize_row_q8_0_reference): 8 lanes per 32-block
+    // Q8_0 (quantize_row_q8_0's AVX2 path, as quantize_q80_kernel): 8 lanes per 32-block
     for (int blk = tid >> 3; blk < K / 32; blk += 32) {
         const int d4 = blk * 32 + (tid & 7) * 4;
         float4 v = *reinterpret_cast<const float4 *>(xf + d4);
@@ -1377,8 +1377,8 @@ __global__ __launch_bounds__(256) void dec_head_kernel(const float *__restrict__
         float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
         amax = group8_max(amax);
         const float dd = amax / 127.0f;
-        const float id = dd != 0.0f ? 1.0f / dd : 0.0f;
-        const int a0 = (int)roundf(v.x * id), a1 = (int)roundf(v.y * id), a2 = (int)roundf(v.z * id), a3 = (int)roundf(v.w * id);
+        const float id = amax != 0.0f ? 127.0f / amax : 0.0f;
+        const int a0 = (int)rintf(v.x * id), a1 = (int)rintf(v.y * id), a2 = (int)rintf(v.z * id), a3 = (int)rintf(v.w * id);
         *reinterpret_cast<uint32_t *>(xq + d4) = (uint32_t)(a0 & 0xff) | ((uint32_t)(a1 & 0xff) << 8) | ((uint32_t)(a2 & 0xff) << 16) | ((uint32_t)(a3 & 0xff) << 24);
         if ((tid & 7) == 0) xdd[blk] = h2f(f2h(dd));
     }

@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256) void quantize_q8k_kernel(const float *__restri
     wave_quant_q8k(v, lane, qs + blk * 256, d + blk, bsums + blk * 16);
 }
 
-// quantize_row_q8_0_reference (ggml QuantizeQ8.cpp:32-55): d = amax/127 (stored fp16), q = roundf(x * (1/d)).
+// quantize_row_q8_0 as the reference's x86 build runs it, the AVX2 path (ggml QuantizeQ8.cpp:113-167), not quantize_row_q8_0_reference:
+// d = amax/127 (stored fp16), q = rint(x * (127/amax)) -- _mm256_round_ps(_MM_ROUND_NEAREST) takes halves to even.
 // One lane per 32-block would serialise; use 8 lanes per block (4 values each), 8 blocks per wave.
 __global__ __launch_bounds__(256) void quantize_q80_kernel(const float *__restrict__ x, int8_t *__restrict__ qs, uint16_t *__restrict__ d, int64_t n_blocks) {
     const int lane = threadIdx.x & 63;
@@ -99,10 +100,10 @@ __global__ __launch_bounds__(256) void quantize_q80_kernel(const float *__restri
     float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     amax = group8_max(amax);
     const float dd = __fdiv_rn(amax, 127.0f);
-    const float id = dd != 0.0f ? __fdiv_rn(1.0f, dd) : 0.0f;
+    const float id = amax != 0.0f ? __fdiv_rn(127.0f, amax) : 0.0f;
     if (!ok) return;
-    const int q0 = (int)roundf(__fmul_rn(v.x, id)), q1 = (int)roundf(__fmul_rn(v.y, id));
-    const int q2 = (int)roundf(__fmul_rn(v.z, id)), q3 = (int)roundf(__fmul_rn(v.w, id));
+    const int q0 = (int)rintf(__fmul_rn(v.x, id)), q1 = (int)rintf(__fmul_rn(v.y, id));
+    const int q2 = (int)rintf(__fmul_rn(v.z, id)), q3 = (int)rintf(__fmul_rn(v.w, id));
     const uint32_t packed = (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
     reinterpret_cast<uint32_t *>(qs + blk * 32)[lane & 7] = packed;
     if ((lane & 7) == 0) d[blk] = f2h(dd);

@@ -173,13 +173,14 @@ def quantized_blocks(dtype: int, rng: np.random.Generator, n_elem: int, std: flo
     raise ValueError(f"no quantised-domain synthesiser for dtype {dtype}")
 
 
-def tensor_stored(name: str, shape: Tuple[int, ...], kind: str, target: int = mf.Q4_K) -> Tuple[int, np.ndarray]:
-    """(storage dtype, bytes / fp32 values) of one synthetic tensor as a `*-q4_k.mllm` (or fp32) file holds it."""
+def tensor_stored(name: str, shape: Tuple[int, ...], kind: str, target: int = mf.Q4_K, full_range: bool = False) -> Tuple[int, np.ndarray]:
+    """(storage dtype, bytes / fp32 values) of one synthetic tensor as a `*-q4_k.mllm` (or fp32) file holds it.
+    full_range draws the quantised tensors over every field's whole range (q4k_blocks / q40_blocks); fp32 tensors do not depend on it."""
     dt = storage_dtype(name, target)
     if dt == mf.F32:
         return dt, tensor_f32(name, shape, kind)
     rng = np.random.default_rng(SEED0 + zlib.crc32(name.encode()))
-    return dt, quantized_blocks(dt, rng, int(np.prod(shape)))
+    return dt, quantized_blocks(dt, rng, int(np.prod(shape)), full_range=full_range)
 
 
 def qwen2vl_tensors(c: Qwen2VLConfig, vision: bool = True) -> Iterator[Tuple[str, Tuple[int, ...], str]]:

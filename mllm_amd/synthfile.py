@@ -17,17 +17,21 @@ from . import mllmfile as mf, synth
 TAG = "q4k-qd1"      # file-name tag of the synthesis scheme (quantised-domain draw, version 1): a cached file of another scheme is never picked up
 
 
+FULL_RANGE_TAG = "-fr"   # file-name tag of a full-range draw (synth.q4k_blocks(full_range=True)): the two kinds never share a cached file
+
+
 def _make_tensor(args):
-    name, shape, kind, target = args
-    dt, data = synth.tensor_stored(name, shape, kind, target)
+    name, shape, kind, target, full_range = args
+    dt, data = synth.tensor_stored(name, shape, kind, target, full_range)
     return name, dt, data
 
 
-def build_q4k_file(path: str, specs, target: int = mf.Q4_K, workers: int | None = None) -> str:
+def build_q4k_file(path: str, specs, target: int = mf.Q4_K, workers: int | None = None, full_range: bool = False) -> str:
     """Synthesise every tensor and write the .mllm.  Tensors are made by a thread pool (numpy's Generator and array arithmetic release the GIL);
-    the output bytes do not depend on `workers`."""
-    jobs = [(n, s, k, target) for n, s, k in specs]
-    total = sum(int(np.prod(s)) for _, s, _, _ in jobs)
+    the output bytes do not depend on `workers`.  full_range: quantised tensors drawn over every field's whole range (the default draw, the bench
+    workload, makes every model collapse onto a single greedy id; this one does not)."""
+    jobs = [(n, s, k, target, full_range) for n, s, k in specs]
+    total = sum(int(np.prod(s)) for _, s, _, _, _ in jobs)
     if workers is None:
         workers = min(16, os.cpu_count() or 1)
     tmp = path + f".tmp{os.getpid()}"
@@ -42,12 +46,13 @@ def build_q4k_file(path: str, specs, target: int = mf.Q4_K, workers: int | None 
     return path
 
 
-def qwen2vl_file(cfg: synth.Qwen2VLConfig, cache_dir: str = "/tmp/mllm_amd_cache", tag: str = "", vision: bool = True) -> str:
+def qwen2vl_file(cfg: synth.Qwen2VLConfig, cache_dir: str = "/tmp/mllm_amd_cache", tag: str = "", vision: bool = True, full_range: bool = False) -> str:
     os.makedirs(cache_dir, exist_ok=True)
-    key = f"q2vl-h{cfg.hidden}-i{cfg.inter}-l{cfg.layers}-v{cfg.vocab}-vd{cfg.v_dim}-vb{cfg.v_blocks}{'' if vision else '-novis'}{'' if cfg.tie_embedding else '-untied'}{tag}-{TAG}.mllm"
+    key = (f"q2vl-h{cfg.hidden}-i{cfg.inter}-l{cfg.layers}-v{cfg.vocab}-vd{cfg.v_dim}-vb{cfg.v_blocks}{'' if vision else '-novis'}{'' if cfg.tie_embedding else '-untied'}{tag}"
+           f"{FULL_RANGE_TAG if full_range else ''}-{TAG}.mllm")
     path = os.path.join(cache_dir, key)
     if not os.path.exists(path):
-        build_q4k_file(path, synth.qwen2vl_tensors(cfg, vision=vision))
+        build_q4k_file(path, synth.qwen2vl_tensors(cfg, vision=vision), full_range=full_range)
     return path
 
 
@@ -58,13 +63,15 @@ def tensor_digests(path: str) -> dict:
     return out
 
 
-def causal_lm_file(cfg: synth.CausalLMConfig, cache_dir: str = "/tmp/mllm_amd_cache") -> str:
+def causal_lm_file(cfg: synth.CausalLMConfig, cache_dir: str = "/tmp/mllm_amd_cache", full_range: bool = False) -> str:
     os.makedirs(cache_dir, exist_ok=True)
+    if full_range and cfg.target == mf.F32:
+        raise ValueError("full_range draws quantised tensors; an fp32 file has none")
     key = (f"{cfg.family}-h{cfg.hidden}-i{cfg.inter}-l{cfg.layers}-a{cfg.heads}k{cfg.kv_heads}-v{cfg.vocab}-t{int(cfg.tie_embedding)}"
-           f"-{'f32' if cfg.target == mf.F32 else TAG}.mllm")
+           f"{FULL_RANGE_TAG if full_range else ''}-{'f32' if cfg.target == mf.F32 else TAG}.mllm")
     path = os.path.join(cache_dir, key)
     if not os.path.exists(path):
-        build_q4k_file(path, synth.causal_lm_tensors(cfg), target=cfg.target)
+        build_q4k_file(path, synth.causal_lm_tensors(cfg), target=cfg.target, full_range=full_range)
     return path
 
 

@@ -5,6 +5,8 @@ oracle/Makefile.ref from /root/reference).  Runs only in the development contain
 
     make -f oracle/Makefile.ref -j8 && python oracle/make_golden.py [--full]          # op goldens + tiny Qwen2-VL (+ the 2 B runs)
     python oracle/make_golden.py --all [--full]                                          # every golden that depends on a synthetic model file
+    python oracle/make_golden.py --informative                                           # the goldens on the full-range toy files (ids that change)
+    python oracle/make_golden.py --full-long                                             # the 2 B runs that decode past T = 512
 
 Op-level cases store their inputs (fp32), the raw weight bytes the reference consumed (written by the reference's own `quantize` tool from seeded fp32 arrays)
 and the reference's outputs, so the tests replay them without the reference.  Model-level cases run the reference on the synthetic `.mllm` files of
@@ -12,11 +14,13 @@ mllm_amd/synthfile.py (Q4_K / Q4_0 tensors drawn directly in the quantised domai
 """
 from __future__ import annotations
 
+import io
 import json
 import os
 import subprocess
 import sys
 import tempfile
+import zipfile
 
 import numpy as np
 
@@ -251,41 +255,70 @@ def _cfg_q2vl(c):
             f"{c.vision_end_token_id},{c.video_token_id}")
 
 
+# the 2 B image run covers the whole plain bench workload (prefill + 256 greedy steps); the prompt is 282 tokens, so steps 166 / 167 and 230 / 231 decode at T = 448 / 449
+# (the decode attention's LDS ring wraps) and T = 512 / 513 (its second score pass).  Steps 16 / 48 / 64 are kept so the file stays a superset of its 65-step predecessor.
+FULL_STEPS = 257
+FULL_SAMPLED = tuple(sorted(set(range(0, 257, 32)) | {16, 48, 64, 166, 167, 230, 231}))
+# the long 2 B text run: LONG2B_PROMPT tokens + 128 steps; steps 28 / 29 and 92 / 93 decode at T = 448 / 449 and 512 / 513
+LONG2B_PROMPT, LONG2B_STEPS = 420, 129
+LONG2B_SAMPLED = tuple(sorted(set(range(0, 129, 16)) | {28, 29, 92, 93}))
+
+
+def _run_2b(path, c, ids_, steps, sampled, pix=None):
+    """The reference's Qwen2-VL-2B on `path`: greedy ids, and the top-64 / every-97th logits (_sampled) of the steps in `sampled`."""
+    td = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP"))
+    ids_.astype(np.int32).tofile(os.path.join(td, "ids.i32"))
+    every = int(np.gcd.reduce(np.array(sampled)))       # the driver dumps every `every`-th step's logits (and the last)
+    cmd = [os.path.join(REF, "ref_qwen2vl"), "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "8", "--out", td, "--cfg", _cfg_q2vl(c),
+           "--dump-every", str(every)]
+    if pix is not None:
+        pix.tofile(os.path.join(td, "pix.f32"))
+        cmd += ["--pix", os.path.join(td, "pix.f32"), "--grid", "1,32,32"]
+    out = subprocess.run(cmd, check=True, capture_output=True, text=True)
+    toks = np.fromfile(os.path.join(td, "tokens.i32"), dtype=np.int32)
+    ti, tv, st = _sampled(np.stack([np.fromfile(os.path.join(td, f"logits_{s_}.f32"), dtype=np.float32) for s_ in sampled]))
+    return toks, np.array(sampled, dtype=np.int32), ti, tv, st, out.stdout.strip().splitlines()[0]
+
+
 def e2e_full():
-    """The full-size (Qwen2-VL-2B shaped) reference runs on the synthetic file: (1) 448 x 448 image + 24 tokens, 65 greedy steps: ids, and of steps 0 / 16 / 32 / 48 / 64
-    the top-64 logits and every 97th; (2) a 40-token text prompt, 33 steps, steps 0 / 8 / .. / 32 likewise; (3) the vision tower's image_embeds, all 256 x 1536."""
+    """The full-size (Qwen2-VL-2B shaped) reference runs on the synthetic file: (1) 448 x 448 image + 24 tokens, FULL_STEPS greedy steps: ids, and of the steps FULL_SAMPLED
+    the top-64 logits and every 97th; (2) a 40-token text prompt, 33 steps, steps 0 / 8 / .. / 32 likewise; (3) the vision tower's image_embeds, all 256 x 1536;
+    (4) e2e_full_long."""
     c = synth.qwen2vl_2b()
     path = weights.qwen2vl_file(c, cache_dir=CACHE)
-    pix, grid, ids = synth.qwen2vl_inputs(c, (32, 32), 24)
-
-    def run(ids_, steps, every, with_img):
-        td = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP"))
-        ids_.astype(np.int32).tofile(os.path.join(td, "ids.i32"))
-        cmd = [os.path.join(REF, "ref_qwen2vl"), "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "8", "--out", td, "--cfg", _cfg_q2vl(c),
-               "--dump-every", str(every)]
-        if with_img:
-            pix.tofile(os.path.join(td, "pix.f32"))
-            cmd += ["--pix", os.path.join(td, "pix.f32"), "--grid", "1,32,32"]
-        out = subprocess.run(cmd, check=True, capture_output=True, text=True)
-        toks = np.fromfile(os.path.join(td, "tokens.i32"), dtype=np.int32)
-        dumped = sorted(int(f[7:-4]) for f in os.listdir(td) if f.startswith("logits_") and int(f[7:-4]) % every == 0)
-        ti, tv, st = _sampled(np.stack([np.fromfile(os.path.join(td, f"logits_{s_}.f32"), dtype=np.float32) for s_ in dumped]))
-        return toks, np.array(dumped, dtype=np.int32), ti, tv, st, out.stdout.strip().splitlines()[0]
-
-    toks, steps, ti, tv, st, timing = run(ids, 65, 16, True)
-    np.savez_compressed(os.path.join(GOLD, "qwen2vl_2b_ref.npz"), tokens=toks, steps=steps, top_idx=ti, top_val=tv, strided=st, timing=np.frombuffer(timing.encode(), dtype=np.uint8))
-    print("qwen2vl_2b_ref.npz", toks[:8], steps, timing)
+    pix, grid, _ = synth.qwen2vl_inputs(c, (32, 32), 24)
+    e2e_full_image()
     ids_t = np.random.default_rng(5).integers(0, 150000, size=40).astype(np.int32)
-    toks, steps, ti, tv, st, timing = run(ids_t, 33, 8, False)
+    toks, steps, ti, tv, st, timing = _run_2b(path, c, ids_t, 33, tuple(range(0, 33, 8)))
     np.savez_compressed(os.path.join(GOLD, "qwen2vl_2b_ref_text.npz"), ids=ids_t, tokens=toks, steps=steps, top_idx=ti, top_val=tv, strided=st)
     print("qwen2vl_2b_ref_text.npz", toks[:8], steps, timing)
     (emb,), _ = run_ops("vision", path, [[(pix, (1024, 3, 2, 14, 14)), (grid.astype(np.float32), (1, 1, 1, 3))]], p=(c.hidden, c.v_dim), threads=8)
     np.savez_compressed(os.path.join(GOLD, "qwen2vl_2b_ref_vision.npz"), image_embeds=emb.reshape(-1, c.hidden))
     print("qwen2vl_2b_ref_vision.npz", emb.reshape(-1, c.hidden).shape)
+    e2e_full_long()
 
 
-def run_ref_llm(c, n_prompt, steps, threads=4):
-    td, path = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP")), weights.causal_lm_file(c, CACHE)
+def e2e_full_image():
+    c = synth.qwen2vl_2b()
+    path = weights.qwen2vl_file(c, cache_dir=CACHE)
+    pix, grid, ids = synth.qwen2vl_inputs(c, (32, 32), 24)
+    toks, steps, ti, tv, st, timing = _run_2b(path, c, ids, FULL_STEPS, FULL_SAMPLED, pix)
+    savez_stable(os.path.join(GOLD, "qwen2vl_2b_ref.npz"), tokens=toks, steps=steps, top_idx=ti, top_val=tv, strided=st)      # no timing: a rerun writes the same bytes
+    print("qwen2vl_2b_ref.npz", _id_stats(toks), toks[:8], steps, timing)
+
+
+def e2e_full_long():
+    """A 2 B text prompt of LONG2B_PROMPT tokens + 128 greedy steps, so the ids past T = 448 and T = 512 are the reference's: ids, and the sampled logits of LONG2B_SAMPLED."""
+    c = synth.qwen2vl_2b()
+    path = weights.qwen2vl_file(c, cache_dir=CACHE)
+    ids_l = np.random.default_rng(29).integers(0, 150000, size=LONG2B_PROMPT).astype(np.int32)
+    toks, steps, ti, tv, st, timing = _run_2b(path, c, ids_l, LONG2B_STEPS, LONG2B_SAMPLED)
+    savez_stable(os.path.join(GOLD, "qwen2vl_2b_ref_long.npz"), ids=ids_l, tokens=toks, steps=steps, top_idx=ti, top_val=tv, strided=st)
+    print("qwen2vl_2b_ref_long.npz", _id_stats(toks), toks[:8], steps, timing)
+
+
+def run_ref_llm(c, n_prompt, steps, threads=4, full_range=False):
+    td, path = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP")), weights.causal_lm_file(c, CACHE, full_range=full_range)
     ids = synth.causal_lm_ids(c, n_prompt)
     ids.tofile(os.path.join(td, "ids.i32"))
     cfg = f"{c.hidden},{c.inter},{c.layers},{c.heads},{c.kv_heads},{c.vocab},{c.cache_limit},{int(c.tie_embedding)}"
@@ -294,6 +327,87 @@ def run_ref_llm(c, n_prompt, steps, threads=4):
     toks = np.fromfile(os.path.join(td, "tokens.i32"), dtype=np.int32)
     logits = np.stack([np.fromfile(os.path.join(td, f"logits_{s}.f32"), dtype=np.float32) for s in range(steps)])
     return ids, toks, logits, out.stdout.strip().splitlines()[0]
+
+
+def nondegenerate(toks, min_distinct=8, min_changes=12):
+    """The bar every informative golden of >= 24 steps clears: >= 8 distinct greedy ids, and an id that differs from its predecessor at >= 12 steps."""
+    t = np.asarray(toks)
+    return len(np.unique(t)) >= min_distinct and int(np.count_nonzero(t[1:] != t[:-1])) >= min_changes
+
+
+def _id_stats(toks):
+    t = np.asarray(toks)
+    return f"{len(t)} ids, {len(np.unique(t))} distinct, {int(np.count_nonzero(t[1:] != t[:-1]))} changes"
+
+
+def _ref_q2vl(path, c, ids, steps, pix=None, grid=None, untied=False):
+    """The reference's Qwen2-VL on `path`: greedy ids (prefill + steps - 1 decode steps) and every step's logits."""
+    td = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP"))
+    ids.astype(np.int32).tofile(os.path.join(td, "ids.i32"))
+    cmd = [os.path.join(REF, "ref_qwen2vl"), "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "4", "--out", td,
+           "--cfg", _cfg_q2vl(c) + (",0" if untied else ""), "--dump-every", "1"]
+    if pix is not None:
+        pix.tofile(os.path.join(td, "pix.f32"))
+        cmd += ["--pix", os.path.join(td, "pix.f32"), "--grid", ",".join(str(int(v)) for v in grid)]
+    subprocess.run(cmd, check=True, capture_output=True)
+    toks = np.fromfile(os.path.join(td, "tokens.i32"), dtype=np.int32)
+    return toks, np.stack([np.fromfile(os.path.join(td, f"logits_{s}.f32"), dtype=np.float32) for s in range(steps)])
+
+
+# run (c) of qwen2vl_tiny_fr.npz: a 430-token text prompt + 120 greedy steps at cache_limit 800, so the decode attention passes T = 448 / 449 (its LDS ring wraps,
+# steps 18 / 19) and T = 512 / 513 (a second score pass, steps 82 / 83); every logit of these steps is kept
+LONG_PROMPT, LONG_STEPS = 430, 120
+LONG_LOGIT_STEPS = (0, 12, 18, 19, 24, 36, 48, 60, 72, 82, 83, 96, 108, 119)
+
+
+def savez_stable(path, **arrays):
+    """np.savez_compressed with a fixed time stamp on every member, so that a rerun writes the same bytes (numpy stamps each member with the current time)."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(zi, buf.getvalue())
+
+
+def informative_ids_text(n, vocab=2000):
+    return (np.arange(n, dtype=np.int64) * 7919 % vocab).astype(np.int32)
+
+
+def informative_tiny():
+    """Goldens on the full-range draw of the toy files (synthfile FULL_RANGE_TAG), whose greedy ids change from step to step -- unlike the default draw, where every
+    model collapses onto one id.  qwen2vl_tiny_fr.npz: (a) the 8 x 8 image + 6-token prompt, 40 steps; (b) a 40-token text prompt, 40 steps; (c) the long run
+    (LONG_PROMPT tokens + LONG_STEPS steps, cache_limit 800): all ids, every logit of LONG_LOGIT_STEPS; (d) the untied head, image prompt, 24 steps.
+    configs_tiny_fr.npz: Qwen1.5 and TinyLlama (Q4_K) toys, 20-token prompt, 32 steps.  Every run clears nondegenerate()."""
+    c = synth.qwen2vl_tiny()
+    path = weights.qwen2vl_file(c, cache_dir=CACHE, full_range=True)
+    pix, grid, ids = synth.qwen2vl_inputs(c, (8, 8), 6)
+    out = {"ids": ids, "grid": grid}
+    out["tokens"], out["logits"] = _ref_q2vl(path, c, ids, 40, pix, grid)
+    out["ids_text"] = informative_ids_text(40)
+    out["tokens_text"], out["logits_text"] = _ref_q2vl(path, c, out["ids_text"], 40)
+    cl = synth.qwen2vl_tiny()
+    cl.cache_limit = 800
+    out["ids_long"] = np.random.default_rng(23).integers(0, 2000, size=LONG_PROMPT).astype(np.int32)
+    out["tokens_long"], lg = _ref_q2vl(path, cl, out["ids_long"], LONG_STEPS)
+    out["long_steps"] = np.array(LONG_LOGIT_STEPS, dtype=np.int32)
+    out["logits_long"] = lg[list(LONG_LOGIT_STEPS)]
+    cu = synth.qwen2vl_tiny()
+    cu.tie_embedding = False
+    out["tokens_untied"], out["logits_untied"] = _ref_q2vl(weights.qwen2vl_file(cu, cache_dir=CACHE, full_range=True), cu, ids, 24, pix, grid, untied=True)
+    for k in ("tokens", "tokens_text", "tokens_long", "tokens_untied"):
+        print("qwen2vl_tiny_fr.npz", k, _id_stats(out[k]), out[k][:12].tolist())
+        assert nondegenerate(out[k]), (k, out[k].tolist())
+    savez_stable(os.path.join(GOLD, "qwen2vl_tiny_fr.npz"), **out)
+    G = {}
+    for pre, c in (("qwen", synth.qwen15_tiny()), ("tlq", synth.tinyllama_tiny(mf.Q4_K))):
+        G[pre + "_ids"], G[pre + "_tokens"], G[pre + "_logits"], _ = run_ref_llm(c, 20, 32, full_range=True)
+        print("configs_tiny_fr.npz", pre, _id_stats(G[pre + "_tokens"]), G[pre + "_tokens"][:12].tolist())
+        assert nondegenerate(G[pre + "_tokens"]), (pre, G[pre + "_tokens"].tolist())
+    savez_stable(os.path.join(GOLD, "configs_tiny_fr.npz"), **G)
+    for f in ("qwen2vl_tiny_fr.npz", "configs_tiny_fr.npz"):
+        print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
 
 
 def run_ref_vit(c, n_img, threads=4):
@@ -596,8 +710,16 @@ if __name__ == "__main__":
     if "--llava-full" in sys.argv:
         llava_full()
         sys.exit(0)
+    if "--full-long" in sys.argv:      # only the 2 B runs that decode past T = 512: the image prompt's and the long text prompt's
+        e2e_full_image()
+        e2e_full_long()
+        sys.exit(0)
+    if "--informative" in sys.argv:
+        informative_tiny()
+        sys.exit(0)
     if "--all" in sys.argv:      # every golden that depends on a synthetic model file
         e2e_tiny()
+        informative_tiny()
         e2e_ragged()
         configs_tiny()
         llava_tiny()

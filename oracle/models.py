@@ -133,7 +133,10 @@ class LLM:
             if stages is not None:
                 stages[f"layer{i}"] = x.copy()
         x = orc.rmsnorm(x[-1:], w.v("model.norm.weight"), c.rms_eps)
-        logits = orc.linear(x, w.f.raw(emb_name), w.f.dtype(emb_name), c.vocab)
+        if c.tie_embedding:
+            logits = orc.linear(x, w.f.raw(emb_name), w.f.dtype(emb_name), c.vocab)
+        else:       # a separate lm_head Linear (modeling_qwen2_vl.hpp:375-401)
+            logits = w.lin(x, "lm_head", c.vocab, bias=False)
         self.last_pos = float(pos.max())
         return logits[0]
 

@@ -77,16 +77,18 @@ void orc_quantize_row_q8_K(const float *x, void *vy, int k) {
     }
 }
 
+/* quantize_row_q8_0, the AVX2 path the reference's x86 build runs (QuantizeQ8.cpp:113-167), not its scalar quantize_row_q8_0_reference:
+ * the multiplier is 127 / amax (not 1 / (amax / 127)) and _mm256_round_ps(_MM_ROUND_NEAREST) rounds halves to even (rintf, not roundf) */
 void orc_quantize_row_q8_0(const float *x, void *vy, int k) {
     block_q8_0 *y = (block_q8_0 *)vy;
     const int nb = k / QK8_0;
     for (int i = 0; i < nb; i++) {
         float amax = 0.0f;
         for (int j = 0; j < QK8_0; j++) { float v = fabsf(x[i * QK8_0 + j]); amax = amax > v ? amax : v; }
-        const float d = amax / ((1 << 7) - 1);
-        const float id = d ? 1.0f / d : 0.0f;
+        const float d = amax / 127.f;
+        const float id = amax != 0.0f ? 127.f / amax : 0.0f;
         y[i].d = orc_f32_to_f16(d);
-        for (int j = 0; j < QK8_0; ++j) y[i].qs[j] = roundf(x[i * QK8_0 + j] * id);
+        for (int j = 0; j < QK8_0; ++j) y[i].qs[j] = (int8_t)rintf(x[i * QK8_0 + j] * id);
     }
 }
 

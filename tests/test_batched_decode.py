@@ -96,3 +96,66 @@ def test_batched_rows_linear_head_and_b2():
     with pytest.raises(lib.MllmHipError):
         m.batch_begin(16)
     m.close()
+
+
+def test_batched_rows_equal_the_reference_on_the_full_range_file():
+    """B = 4 on the full-range toy file (tests/golden/qwen2vl_tiny_fr.npz), whose greedy ids change every step, so rows fed each other's (or a stale) token cannot pass: the
+    image and text prompts of the golden give the reference's ids and logits, the two other rows their batch-1 runs."""
+    from mllm_amd import lib
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qwen2vl_tiny_fr.npz"))
+    cfg = synth.qwen2vl_tiny()
+    path = weights.qwen2vl_file(cfg, CACHE, full_range=True)
+    pix, grid, ids_img = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    r = np.random.default_rng(78)
+    prompts = [(ids_img, pix, grid), (g["ids_text"], None, None), (r.integers(0, 2000, size=9).astype(np.int32), None, None),
+               (r.integers(0, 2000, size=17).astype(np.int32), None, None)]
+    steps = len(g["tokens"]) - 1
+    want = [(g["tokens"].tolist(), g["logits"]), (g["tokens_text"].tolist(), g["logits_text"])]
+    want += [_alone(lib, cfg, path, p, steps, im, me) for p, im, me in prompts[2:]]
+    m = lib.Model(cfg, path)
+    B = len(prompts)
+    m.batch_begin(B)
+    cur = []
+    for b, (p, im, me) in enumerate(prompts):
+        m.batch_select(b)
+        tok, lg, _ = m.prefill(p, im, me)
+        assert tok == want[b][0][0] and np.array_equal(lg, want[b][1][0]), b
+        cur.append(tok)
+    for s in range(1, steps + 1):
+        nxt, lg, _ = m.batch_decode(cur)
+        for b in range(B):
+            assert int(nxt[b]) == want[b][0][s], (s, b)
+            assert np.array_equal(lg[b], want[b][1][s]), (s, b, float(np.abs(lg[b] - want[b][1][s]).max()))
+        cur = nxt.tolist()
+    m.close()
+
+
+def test_batched_rows_linear_head_b2_b3_on_the_full_range_file():
+    """TinyLlama (Q4_K, Linear head) on its full-range file: the golden prompt's row equals the reference (tests/golden/configs_tiny_fr.npz), two other rows their
+    batch-1 runs, stepping as B = 2 (the third waits), then B = 3."""
+    from mllm_amd import lib
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "configs_tiny_fr.npz"))
+    cfg = synth.tinyllama_tiny(mf.Q4_K)
+    path = weights.causal_lm_file(cfg, CACHE, full_range=True)
+    r = np.random.default_rng(6)
+    prompts = [g["tlq_ids"]] + [r.integers(0, cfg.vocab, size=n).astype(np.int32) for n in (6, 11)]
+    steps = 12
+    want = [(g["tlq_tokens"].tolist(), g["tlq_logits"])] + [_alone(lib, cfg, path, p, steps) for p in prompts[1:]]
+    m = lib.Model(cfg, path)
+    m.batch_begin(3)
+    cur = []
+    for b, p in enumerate(prompts):
+        m.batch_select(b)
+        tok, lg, _ = m.prefill(p)
+        assert tok == want[b][0][0] and np.array_equal(lg, want[b][1][0]), b
+        cur.append(tok)
+    pos = [0, 0, 0]
+    for s in range(steps):
+        rows = [0, 1] if s < 3 else [0, 1, 2]           # B = 2 for three steps (sequence 2 waits), then B = 3
+        nxt, lg, _ = m.batch_decode([cur[b] for b in rows])
+        for i, b in enumerate(rows):
+            pos[b] += 1
+            assert int(nxt[i]) == want[b][0][pos[b]], (s, b)
+            assert np.array_equal(lg[i], want[b][1][pos[b]]), (s, b, float(np.abs(lg[i] - want[b][1][pos[b]]).max()))
+            cur[b] = int(nxt[i])
+    m.close()

@@ -171,7 +171,7 @@ def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path, monkeypa
 def test_plain_bench_times_exactly_the_steps_asked_for_and_dumps_their_ids(tmp_path):
     """A plain run (no --full) times exactly --steps greedy steps, also past the end of the KV slab (800 tokens: 282 of prompt + 2 of warmup leave room for 515, the
     other 85 run after an untimed prefill of the same prompt), leaves the extras null, and --dump-outputs writes the ids those steps produced: the reference's greedy
-    ids of the same prompt on the same file (tests/golden/qwen2vl_2b_ref.npz: the prefill's id, then 64 steps) from step W + 1 on, and from step 1 on in the second segment."""
+    ids of the same prompt on the same file (tests/golden/qwen2vl_2b_ref.npz: the prefill's id, then 256 steps) from step W + 1 on, and from step 1 on in the second segment."""
     import numpy as np
     d = tmp_path / "out"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "600", "--warmup", "2", "--dump-outputs", str(d)],
@@ -189,4 +189,4 @@ def test_plain_bench_times_exactly_the_steps_asked_for_and_dumps_their_ids(tmp_p
     assert t.dtype == np.float64 and t.shape == (600,)
     g = np.load(os.path.join(ROOT, "tests", "golden", "qwen2vl_2b_ref.npz"))["tokens"]
     room = 800 - 282 - 2 - 1
-    assert np.array_equal(t[:62], g[3:]) and np.array_equal(t[room:room + 64], g[1:])
+    assert len(g) == 257 and np.array_equal(t[:254], g[3:]) and np.array_equal(t[room:600], g[1:86])

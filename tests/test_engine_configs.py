@@ -56,10 +56,21 @@ LM_CASES = [("qwen", synth.qwen15_tiny), ("tlq", lambda: synth.tinyllama_tiny(mf
 @pytest.mark.gpu
 @pytest.mark.parametrize("key,mk", LM_CASES, ids=[c[0] for c in LM_CASES])
 def test_engine_causal_lm_tiny_matches_reference(key, mk):
+    _engine_causal_lm_matches("configs_tiny.npz", key, mk, False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key,mk", LM_CASES, ids=[c[0] for c in LM_CASES])
+def test_engine_causal_lm_tiny_full_range_matches_reference(key, mk):
+    """The same on the full-range files (tests/golden/configs_tiny_fr.npz), where the reference's greedy id changes from step to step."""
+    _engine_causal_lm_matches("configs_tiny_fr.npz", key, mk, True)
+
+
+def _engine_causal_lm_matches(gold_name, key, mk, full_range):
     from mllm_amd import lib
-    gold = np.load(os.path.join(GOLD, "configs_tiny.npz"))
+    gold = np.load(os.path.join(GOLD, gold_name))
     cfg = mk()
-    m = lib.Model(cfg, weights.causal_lm_file(cfg, CACHE))
+    m = lib.Model(cfg, weights.causal_lm_file(cfg, CACHE, full_range=full_range))
     toks, logits = m.greedy(gold[key + "_ids"], len(gold[key + "_tokens"]))
     assert toks == gold[key + "_tokens"].tolist()
     for s, (lg, ref) in enumerate(zip(logits, gold[key + "_logits"])):

@@ -128,7 +128,7 @@ def test_untied_lm_head_through_the_boundary(tiny, tiny_gold, tmp_path, engine):
 
 def test_reference_module_at_the_2b_geometry(tmp_path):
     """The same, at BASELINE's geometry: the reference's Qwen2VLModel (28 layers, hidden 1536, 32 vision blocks) on the Q4_K file through the adapter, 448 x 448 image + 24 tokens
-    prefilled, 64 decode steps: ids equal the reference's CPU run (tests/golden/qwen2vl_2b_ref.npz) and so do its sampled logits (top 64 + every 97th) at steps 0, 16, 32, 48, 64;
+    prefilled, 256 decode steps: ids equal the reference's CPU run (tests/golden/qwen2vl_2b_ref.npz) and so do its sampled logits (top 64 + every 97th) at the golden's steps;
     no Op falls back.  The driver's report carries the reference's own Module::profiling() numbers (21 ms TTFT, 466 tok/s: the frontend's per-Op host work, 630 Ops per token,
     is the time -- the resident engine behind the same C ABI does 1,118 tok/s)."""
     if not os.path.exists(DRIVER):
@@ -143,7 +143,7 @@ def test_reference_module_at_the_2b_geometry(tmp_path):
     td = str(tmp_path)
     ids.astype(np.int32).tofile(os.path.join(td, "ids.i32"))
     pix.astype(np.float32).tofile(os.path.join(td, "pix.f32"))
-    cmd = [DRIVER, "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "4", "--out", td, "--cfg", _cfg_string(cfg), "--dump-every", "16",
+    cmd = [DRIVER, "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "4", "--out", td, "--cfg", _cfg_string(cfg), "--dump-every", str(int(np.gcd.reduce(g["steps"]))),
            "--pix", os.path.join(td, "pix.f32"), "--grid", ",".join(str(int(x)) for x in grid)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
@@ -178,7 +178,7 @@ def test_engine_module_behind_the_reference_frontend(tiny, tiny_gold, tmp_path):
     td = str(tmp_path)
     ids.astype(np.int32).tofile(os.path.join(td, "ids.i32"))
     pix.astype(np.float32).tofile(os.path.join(td, "pix.f32"))
-    cmd = [DRIVER, "--model", bpath, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "4", "--out", td, "--cfg", _cfg_string(big), "--dump-every", "16",
+    cmd = [DRIVER, "--model", bpath, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps), "--threads", "4", "--out", td, "--cfg", _cfg_string(big), "--dump-every", str(int(np.gcd.reduce(gb["steps"]))),
            "--pix", os.path.join(td, "pix.f32"), "--grid", ",".join(str(int(x)) for x in grid), "--engine", "1"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])

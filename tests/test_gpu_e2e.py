@@ -306,3 +306,139 @@ def test_lane_per_superblock_projection_on_short_rows(tmp_path):
         m.close()
     finally:
         lib.set_option("pjb_min_ns", -1)
+
+
+# ---- the full-range toy file (synthfile full_range=True; tests/golden/qwen2vl_tiny_fr.npz): the reference's greedy id changes from step to step, so a step that embeds a
+# stale id (the previous step's, the prefill's, the captured graph's input) or a launch form that feeds the wrong token cannot pass ------------------------------------
+GOLD_FR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qwen2vl_tiny_fr.npz")
+CACHE = os.environ.get("MLLM_AMD_CACHE", "/tmp/mllm_amd_cache")
+
+
+@pytest.fixture(scope="module")
+def fr_gold():
+    return dict(np.load(GOLD_FR))
+
+
+def _fr_file(cfg):
+    return weights.qwen2vl_file(cfg, cache_dir=CACHE, full_range=True)
+
+
+def _stepwise(m, first, n):
+    """prefill (`first`), then n - 1 single decode steps on the id each step produced: (ids, every logit row)"""
+    tok, logits, _ = first()
+    toks, rows = [tok], [logits]
+    for _ in range(n - 1):
+        tok, logits, _ = m.decode(tok)
+        toks.append(tok)
+        rows.append(logits)
+    return toks, np.stack(rows)
+
+
+def _assert_run(toks, rows, want_toks, want_rows, what):
+    assert toks == want_toks.tolist(), (what, toks, want_toks.tolist())
+    assert np.array_equal(rows, want_rows), (what, [int(s) for s in np.nonzero((rows != want_rows).any(axis=1))[0]], float(np.abs(rows - want_rows).max()))
+
+
+def test_full_range_image_and_text_prompts_match_reference(fr_gold):
+    g = fr_gold
+    cfg = synth.qwen2vl_tiny()
+    pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    assert np.array_equal(ids, g["ids"]) and np.array_equal(grid, g["grid"])
+    m = lib.Qwen2VL(cfg, _fr_file(cfg))
+    try:
+        _assert_run(*_stepwise(m, lambda: m.prefill(ids, pix, grid), len(g["tokens"])), g["tokens"], g["logits"], "image")
+        m.clear_kvcache()
+        _assert_run(*_stepwise(m, lambda: m.prefill(g["ids_text"]), len(g["tokens_text"])), g["tokens_text"], g["logits_text"], "text")
+        m.clear_kvcache()
+        tok, _, _ = m.prefill(g["ids_text"])
+        gen, _ = m.generate(tok, len(g["tokens_text"]) - 1)
+        assert [tok] + gen.tolist() == g["tokens_text"].tolist()
+    finally:
+        m.close()
+
+
+def test_full_range_untied_head_matches_reference(fr_gold):
+    g = fr_gold
+    cfg = synth.qwen2vl_tiny()
+    cfg.tie_embedding = False
+    pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    m = lib.Qwen2VL(cfg, _fr_file(cfg))
+    try:
+        _assert_run(*_stepwise(m, lambda: m.prefill(ids, pix, grid), len(g["tokens_untied"])), g["tokens_untied"], g["logits_untied"], "untied")
+        m.clear_kvcache()
+        tok, _, _ = m.prefill(ids, pix, grid)
+        gen, _ = m.generate(tok, len(g["tokens_untied"]) - 1)
+        assert [tok] + gen.tolist() == g["tokens_untied"].tolist()
+    finally:
+        m.close()
+
+
+def test_full_range_every_merged_launch_form_matches_reference(fr_gold):
+    """merge_o 0..4 (test_merged_attention_and_o_projection_launch_changes_nothing) on ids that change every step: each form twice on the re-armed state, then generate()."""
+    g = fr_gold
+    cfg = synth.qwen2vl_tiny()
+    path = _fr_file(cfg)
+    pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    n = len(g["tokens"])
+    try:
+        for mode in (0, 1, 2, 3, 4):
+            lib.set_option("merge_o", mode)
+            m = lib.Qwen2VL(cfg, path)
+            try:
+                for rep in range(2):
+                    m.clear_kvcache()
+                    _assert_run(*_stepwise(m, lambda: m.prefill(ids, pix, grid), n), g["tokens"], g["logits"], (mode, rep))
+                m.clear_kvcache()
+                tok, _, _ = m.prefill(ids, pix, grid)
+                gen, _ = m.generate(tok, n - 1)
+                assert [tok] + gen.tolist() == g["tokens"].tolist(), mode
+            finally:
+                m.close()
+    finally:
+        lib.set_option("merge_o", -1)
+
+
+def test_full_range_decode_without_the_captured_graph(tmp_path):
+    """MLLM_HIP_NO_GRAPH=1 (own process) on the full-range file: the launches issued one by one give the reference's ids and logits, image and text prompts."""
+    import subprocess
+    import sys
+    code = (
+        "import numpy as np, os, sys\n"
+        "from mllm_amd import lib, synth\n"
+        "from mllm_amd import synthfile as weights\n"
+        "cfg = synth.qwen2vl_tiny()\n"
+        "g = np.load(sys.argv[1])\n"
+        "m = lib.Qwen2VL(cfg, weights.qwen2vl_file(cfg, cache_dir=sys.argv[2], full_range=True))\n"
+        "pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)\n"
+        "for key, first in (('', lambda: m.prefill(ids, pix, grid)), ('_text', lambda: m.prefill(g['ids_text']))):\n"
+        "    m.clear_kvcache()\n"
+        "    tok, logits, _ = first()\n"
+        "    toks, rows = [tok], [logits]\n"
+        "    for s in range(1, 24):\n"
+        "        tok, logits, _ = m.decode(tok); toks.append(tok); rows.append(logits)\n"
+        "    assert toks == g['tokens' + key][:24].tolist() and np.array_equal(np.stack(rows), g['logits' + key][:24]), key\n"
+        "    gen, _ = m.generate(tok, 16)\n"
+        "    assert gen.tolist() == g['tokens' + key][24:40].tolist(), key\n"
+        "print('eager ok')\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code, GOLD_FR, CACHE], capture_output=True, text=True, timeout=600, cwd=root,
+                         env=dict(os.environ, MLLM_HIP_NO_GRAPH="1", PYTHONPATH=root))
+    assert out.returncode == 0 and "eager ok" in out.stdout, (out.stdout[-500:], out.stderr[-2000:])
+
+
+def test_full_range_lane_per_superblock_projection(fr_gold):
+    """pjb_min_ns = 1 (test_lane_per_superblock_projection_on_short_rows) on the full-range file: text and image prompts equal the reference."""
+    g = fr_gold
+    cfg = synth.qwen2vl_tiny()
+    pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    lib.set_option("pjb_min_ns", 1)      # before the model captures its decode graph
+    try:
+        m = lib.Qwen2VL(cfg, _fr_file(cfg))
+        try:
+            _assert_run(*_stepwise(m, lambda: m.prefill(g["ids_text"]), len(g["tokens_text"])), g["tokens_text"], g["logits_text"], "text")
+            m.clear_kvcache()
+            _assert_run(*_stepwise(m, lambda: m.prefill(ids, pix, grid), len(g["tokens"])), g["tokens"], g["logits"], "image")
+        finally:
+            m.close()
+    finally:
+        lib.set_option("pjb_min_ns", -1)

@@ -1,4 +1,5 @@
-"""Full-size GPU parity; NOTE the 2 B goldens hold SAMPLED logits (the top-64 and every 97th logit of steps 0, 16, 32, 48, 64 -- not whole 151,936-wide rows) plus all 65 greedy ids.
+"""Full-size GPU parity; NOTE the 2 B goldens hold SAMPLED logits (the top-64 and every 97th logit of the steps in their `steps` array -- not whole 151,936-wide rows) plus every greedy id
+(qwen2vl_2b_ref.npz: the prefill's id + 256 steps, the plain bench's segment).
 BASELINE.json configs[3] shape (Qwen2-VL-2B, Q4_K, 448x448 image + 24-token prompt, KV limit 800) against golden outputs of the reference's own run on the same synthetic .mllm (tests/golden/qwen2vl_2b_ref*.npz, made by
 oracle/make_golden.py --full from oracle/_ref/ref_qwen2vl / ref_ops): greedy ids identical, every sampled logit bit-identical
 (the goldens keep the top-64 logits and every 97th logit of the dumped steps), the vision tower's image_embeds bit-identical."""
@@ -206,3 +207,72 @@ def test_weight_warming_workgroups_change_nothing_but_time():
             lib.set_option("attn_flags", -1)
     for flags in (91, 251):
         assert runs[flags][0].tolist() == runs[11][0].tolist() and np.array_equal(runs[flags][1], runs[11][1]), flags
+
+
+def test_full_long_text_prompt_past_448_and_512_keys_bit_exact(full_model):
+    """tests/golden/qwen2vl_2b_ref_long.npz: a 420-token text prompt + 128 greedy steps of the reference, whose ids keep changing past T = 448 (the decode attention's LDS
+    ring wraps, steps 28 / 29) and T = 512 (its second score pass, steps 92 / 93): ids and sampled logits stepwise, then generate()."""
+    cfg, m = full_model
+    g = np.load(os.path.join(GOLD, "qwen2vl_2b_ref_long.npz"))
+    assert {28, 29, 92, 93} <= set(g["steps"].tolist())
+    m.clear_kvcache()
+    toks, errs = _run(m, g, lambda: m.prefill(g["ids"]))
+    assert toks == g["tokens"].tolist(), sum(a == b for a, b in zip(toks, g["tokens"].tolist()))
+    assert max(errs) == 0.0, errs
+    m.clear_kvcache()
+    tok, _, _ = m.prefill(g["ids"], want_logits=False)
+    gen, _ = m.generate(tok, len(g["tokens"]) - 1)
+    assert [tok] + gen.tolist() == g["tokens"].tolist()
+
+
+def test_chain_launch_both_qkv_forms_past_512_keys():
+    """chain_cont 0 / 1 (test_chain_launch_qkv_role_carried_on_or_on_its_own_workgroups) on the long 2 B golden, whose ids change at almost every step."""
+    cfg = synth.qwen2vl_2b()
+    path = weights.qwen2vl_file(cfg, cache_dir=os.environ.get("MLLM_AMD_CACHE", "/tmp/mllm_amd_cache"))
+    g = np.load(os.path.join(GOLD, "qwen2vl_2b_ref_long.npz"))
+    try:
+        for mode in (0, 1):
+            lib.set_option("chain_cont", mode)
+            m = lib.Qwen2VL(cfg, path)
+            try:
+                toks, errs = _run(m, g, lambda: m.prefill(g["ids"]))
+                assert toks == g["tokens"].tolist(), mode
+                assert max(errs) == 0.0, (mode, errs)
+            finally:
+                m.close()
+    finally:
+        lib.set_option("chain_cont", -1)
+
+
+@pytest.mark.parametrize("flags", [7, 3, 11, 91, 251])
+def test_decode_attention_forms_match_reference_across_448_and_512_keys(flags):
+    """Run (c) of tests/golden/qwen2vl_tiny_fr.npz: the reference's 430-token prompt + 120 steps at cache_limit 800 on the full-range toy file, so T passes 448 / 449 and
+    512 / 513.  The pipelined attention (7), the unpipelined one (3) and the warming forms (11 / 91 / 251) each give the reference's ids and every stored logit, stepwise
+    and through generate()."""
+    g = np.load(os.path.join(GOLD, "qwen2vl_tiny_fr.npz"))
+    cfg = synth.qwen2vl_tiny()
+    cfg.cache_limit = 800
+    path = weights.qwen2vl_file(cfg, cache_dir=os.environ.get("MLLM_AMD_CACHE", "/tmp/mllm_amd_cache"), full_range=True)
+    want = {int(s): i for i, s in enumerate(g["long_steps"])}
+    assert len(g["ids_long"]) + max(want) >= 513 and {18, 19, 82, 83} <= set(want)
+    lib.set_option("attn_flags", flags)
+    try:
+        m = lib.Qwen2VL(cfg, path)
+        try:
+            tok, logits, _ = m.prefill(g["ids_long"])
+            toks = [tok]
+            assert np.array_equal(logits, g["logits_long"][want[0]])
+            for s in range(1, len(g["tokens_long"])):
+                tok, logits, _ = m.decode(tok)
+                toks.append(tok)
+                if s in want:
+                    assert np.array_equal(logits, g["logits_long"][want[s]]), (s, float(np.abs(logits - g["logits_long"][want[s]]).max()))
+            assert toks == g["tokens_long"].tolist(), [s for s, (a, b) in enumerate(zip(toks, g["tokens_long"].tolist())) if a != b][:5]
+            m.clear_kvcache()
+            tok, _, _ = m.prefill(g["ids_long"])
+            gen, _ = m.generate(tok, len(g["tokens_long"]) - 1)
+            assert [tok] + gen.tolist() == g["tokens_long"].tolist()
+        finally:
+            m.close()
+    finally:
+        lib.set_option("attn_flags", -1)

@@ -64,6 +64,23 @@ def test_quantize_q80_bit_exact(M, K):
     assert eq(d.view(torch.int16), blocks[:, :, :2].copy().view(np.int16).reshape(M, K // 32))
 
 
+def test_quantize_q80_multiplier_and_halves_as_the_reference_x86_build():
+    """The reference's x86 build quantises the tied head's input through quantize_row_q8_0's AVX2 path (QuantizeQ8.cpp:113-167), not its scalar
+    quantize_row_q8_0_reference: the multiplier is 127 / amax and halves round to even.  Block 0 (amax 127, multiplier 1): 2.5 -> 2, -2.5 -> -2, 0.5 -> 0, 126.5 -> 126;
+    block 1 (amax 1.4442534, where 127 / amax and 1 / (amax / 127) differ by an ulp): 0.4264528 * (127 / amax) is 37.5 exactly -> 38, where the other multiplier gives 37."""
+    x = rng(3).standard_normal((2, 96)).astype(np.float32) * 0.1
+    x[0, :8] = [127.0, 2.5, -2.5, 3.5, 0.5, 1.5, -0.5, 126.5]
+    x[0, 32:40] = [1.4442534, 0.4264528, -0.4264528, 0.0, 0.0, 0.0, 0.0, 0.0]
+    x[0, 40:64] = 0.0
+    qs, d = ops.quantize_q80(x)
+    q = qs.cpu().numpy() if hasattr(qs, "cpu") else np.asarray(qs)
+    assert q[0, :8].tolist() == [127, 2, -2, 4, 0, 2, 0, 126]
+    assert q[0, 32:35].tolist() == [127, 38, -38]
+    blocks = orc.quantize_q8_0(x).reshape(2, 3, 34)
+    assert eq(qs, blocks[:, :, 2:].reshape(2, 96).view(np.int8))
+    assert eq(d.view(torch.int16), blocks[:, :, :2].copy().view(np.int16).reshape(2, 3))
+
+
 # ---- A1/A2/A5: Q4_K Linear -----------------------------------------------------------------------------------------------
 def _q4k_case(M, K, N, seed, bias=True):
     r = rng(seed)

@@ -144,3 +144,32 @@ def test_generate_sampled_on_the_engine():
     st = m.memory_stats()
     assert st["released_bytes"] > 0 and st["resident_bytes"] > st["released_bytes"], st
     m.close()
+
+
+@pytest.mark.gpu
+def test_generate_sampled_reproduces_the_reference_ids_that_change():
+    """The full-range toy file (tests/golden/qwen2vl_tiny_fr.npz), whose greedy id changes from step to step: with u = 0 greedy, top-k and top-p all write the reference's ids
+    (a path that kept a stale id or wrote the wrong candidate would repeat or drift), and an eos whose first occurrence is at step >= 3 cuts the run right after that step."""
+    from mllm_amd import synth
+    from mllm_amd import synthfile as weights
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qwen2vl_tiny_fr.npz"))
+    cfg = synth.qwen2vl_tiny()
+    path = weights.qwen2vl_file(cfg, cache_dir=os.environ.get("MLLM_AMD_CACHE", "/tmp/mllm_amd_cache"), full_range=True)
+    pix, grid, ids = synth.qwen2vl_inputs(cfg, (8, 8), 6)
+    want = g["tokens"][1:].tolist()
+    steps = len(want)
+    m = lib.Qwen2VL(cfg, path)
+    try:
+        for method in (0, 1, 2):
+            m.clear_kvcache()
+            tok, _, _ = m.prefill(ids, pix, grid)
+            assert tok == int(g["tokens"][0])
+            got, _ = m.generate_sampled(tok, steps, method, np.zeros(steps, dtype=np.float32))
+            assert got.tolist() == want, (method, got.tolist())
+        cut_at = next(s for s in range(3, steps) if want[s] not in want[:s] and want[s] != int(g["tokens"][0]))
+        m.clear_kvcache()
+        tok, _, _ = m.prefill(ids, pix, grid)
+        cut, _ = m.generate_sampled(tok, steps, 0, np.zeros(steps, dtype=np.float32), eos=want[cut_at])
+        assert cut.size == cut_at + 1 and cut.tolist() == want[:cut_at + 1], (cut_at, cut.tolist())
+    finally:
+        m.close()
