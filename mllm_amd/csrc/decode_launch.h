@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 namespace mllm_hip {
 
@@ -45,30 +46,58 @@ struct DecodeCtx {
     int vt_ld;
     int n_layers;                       // entries of the DecodeLayer array handed to the launchers
     const WeightWarm *warm_tab;         // device, [n_layers] (decode_warm_table), or nullptr: no warming workgroups in the attention launch
-    // merged attention + o-projection launch (option "merge_o"): the attention's output row travels as {value, epoch} pairs, one row per layer, epoch = DecodeState::serial;
+    // shared launches (StepPlan, option "merge_o"): the attention's output row travels as {value, epoch} pairs, one row per layer, epoch = DecodeState::serial;
     // the o-projection's workgroups ride in the attention's launch, fetch their weight rows at once and poll the pairs (profiles/r04_seam_overlap_microbench.md)
     unsigned long long *attn_pairs;     // [n_layers][heads * D], all-ones when the state is armed
     unsigned long long *x_pairs;        // [n_layers][H]: a layer's output row for the next layer's q|k|v role (and the o-projection's residual) when both ride in the down projection's launch (merge_o = 4)
     unsigned long long *qkv_pairs;      // [n_layers][(heads + 2 kv_heads) * D]: q | k | v for the attention role when the q|k|v projection rides in the same launch (merge_o = 3)
     int *poll_err;                      // set when a poll gave up (bounded spins): the step's results are then invalid and the host reports it
-    int merge_o;
-    int attn_flags;                     // decode_attn_flags() as it stood when the model was created: the warming table was built for these, and every launch of this
-                                        // model uses them (option "attn_flags" must be set before mllm_hip_model_create; a later change does not reach a live model)
 };
+
+// ---- the step plan: the launches of one decode step in issue order, decided once per model (decode_step_plan, when the model is created) and issued from there ----
+// A decoder layer is five kernels -- q|k|v, attention, o-projection, gate|up, down -- that run either as launches of their own or as roles of a shared launch: attention +
+// o-projection (STEP_ATTN with o_rows != 0), q|k|v + attention + o-projection (STEP_FRONT), or a layer's down projection + the next layer's q|k|v + attention +
+// o-projection (STEP_CHAIN; never layer 0's roles, whose q|k|v embeds the token).  The plan is the only place where a form is chosen: the launchers take the choice
+// from a StepLaunch, the timing marks take its kind, the warming table asks o_in_attn.  It holds no device pointer, so it outlives a change of the KV slabs in DecodeCtx.
+// The kinds of launch of a step (also what StepMarks reports and mllm_hip_model_time_step sums by): STEP_HEAD = model.norm + lm_head, STEP_NEXT = argmax / state advance
+enum StepKind { STEP_QKV, STEP_ATTN, STEP_OPROJ, STEP_GATEUP, STEP_DOWN, STEP_CHAIN, STEP_FRONT, STEP_HEAD, STEP_NEXT, STEP_KINDS };
+struct StepLaunch {
+    int kind;       // a StepKind
+    int layer;      // the layer of the launch's first role (STEP_CHAIN: the layer of the down projection; the other roles are layer + 1's); unused by STEP_HEAD, STEP_NEXT
+    int persist;    // QKV, GATEUP, HEAD (Linear head): workgroups per CU of the walking / persistent grid, 0 = a workgroup per row group
+    bool blk;       // OPROJ, DOWN: the lane-per-super-block projection dec_proj_blk; GATEUP: the lane-per-super-block dec_gateup_blk; false: the eight-lane kernels
+    int ds;         // ATTN, CHAIN, FRONT: attention workgroups per head (the shared launches: 2)
+    bool pipe;      // ATTN without the o-projection: the pipelined attention kernel (else dec_attn_kernel)
+    int o_rows;     // rows per wave of the o-projection role: 1 in CHAIN and FRONT; ATTN: 1 under merge_o = 2, else 2, and 0 = no o-projection in the attention's launch
+    int cont;       // CHAIN: the q|k|v role is carried on by the first down-projection workgroups (option chain_cont, and a q|k|v grid no larger than the down projection's)
+    int head;       // HEAD: 0 Linear lm_head, 1 tied head by the stand-alone launchers, 2 tied head + partial argmax in one kernel
+    int rows;       // HEAD (form 2): rows per wave
+    int parts;      // HEAD (form 2): workgroups = partial maxima; NEXT: the partial maxima to fold, 0 = an argmax launch over the logits row comes first
+    size_t lds;     // ATTN (pipelined or with the o-projection), CHAIN, FRONT: dynamic LDS bytes of the launch
+};
+// The launch-form options (merge_o, attn_flags, attn_ds, chain_cont, pjb_min_ns, no_pjb, no_gub, gu_persist, qkv_persist, head_wpc) are read by decode_step_plan and nowhere
+// else: a later mllm_hip_set_option does not reach a live model.  What the plan keeps of them is what the engine and the launcher still need.
+struct StepPlan {
+    int merge_o;        // level asked for, 0..4 (default 4: chain; 3: front; 2: attention + o-projection; 1: that with two rows per wave; 0: five launches per layer).
+                        // Non-zero: the engine arms the {value, epoch} pairs and checks poll_err, whichever forms the shapes then allowed
+    int attn_flags;     // bit 0 XCD placement of a K/V group's heads, bit 1 two-stage key fetch (un-pipelined kernel), bit 2 keep the un-pipelined kernel, bit 3 the q|k|v
+                        // projection warms the L2 with the cache rows, bits 4..7 weight-warming workgroups (decode_warm_table).  Default 91
+    bool o_in_attn;     // every layer's o-projection rides in the launch of its attention (ATTN, CHAIN, FRONT): no STEP_OPROJ in the plan
+    std::vector<StepLaunch> launches;      // the step
+    std::vector<StepLaunch> alone;         // [n_layers][5]: kernel STEP_QKV .. STEP_DOWN of a layer as a launch of its own (what the step is made of where nothing merges,
+                                           // and what mllm_hip_model_time_kernel times)
+};
+void decode_step_plan(const DecodeCtx &c, const DecodeLayer *layers, int n_layers, StepPlan *out);
+int decode_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *layers, const StepLaunch &e, hipStream_t st);
 
 // raw Q4_K rows -> decode order: the nibble dwords of every super-block transposed so that a lane's 16 bytes are one column class (q4k_dot.h)
 int decode_order_q4k(const void *src, void *dst, int64_t n_blocks, hipStream_t st);
-int decode_attn_flags();
-bool decode_merges_o(const DecodeCtx &c);      // the step folds the o-projection into the attention's launch (option merge_o and the shapes that form covers)
 int decode_warm_table(const DecodeCtx &c, const DecodeLayer *layers, int n_layers, int flags, WeightWarm *host_out);
-int decode_kernel_launch(const DecodeCtx &c, const DecodeLayer *layers, int li, int which, hipStream_t st);
 int argmax_row_launch(const DecodeCtx &c, const float *logits, int n, int *out, hipStream_t st);      // first-maximum argmax over the chip, partials in c.part_val / c.part_idx
-// Optional marks around every launch of a step (mllm_hip_model_time_step: the step run eagerly with a HIP event either side of each launch).  kind: 0 q|k|v, 1 attention
-// (with the o-projection's workgroups when they ride in it), 2 o-projection, 3 gate|up, 4 down, 5 the chain launch (down + the next layer's q|k|v + attention + o-projection),
-// 6 q|k|v + attention + o-projection as one launch, 7 model.norm + lm_head, 8 argmax / state advance.
-constexpr int STEP_KINDS = 9;
+// The step: a loop over the plan's launches.  Optional marks around every launch (mllm_hip_model_time_step: the step run eagerly with a HIP event either side of each
+// launch); kind = the launch's StepKind.
 struct StepMarks { int (*mark)(void *user, int kind, int after); void *user; };
-int decode_step_launch(const DecodeCtx &c, const DecodeLayer *layers, int n_layers, hipStream_t st, const StepMarks *marks = nullptr);
+int decode_step_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *layers, hipStream_t st, const StepMarks *marks = nullptr);
 
 // ---- batched decode (engine.hip: mllm_hip_model_batch_decode): the one Op of a step that is not row-wise, for all B sequences in one launch each ----
 // one sequence's KV slabs (bases of layer 0) and the tokens its cache holds BEFORE this step

@@ -217,6 +217,7 @@ struct mllm_hip_model {
     int *part_idx = nullptr, *history = nullptr;
     int nsplit = 0, max_parts = 4096, dec_rows = 0;
     DecodeCtx dctx{};
+    StepPlan plan;      // the launches of a decode step (decode_launch.h), decided when the model is created
     std::vector<DecodeLayer> dlayers;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -475,7 +476,7 @@ static int create_impl(M *m, const MllmFile &f) {
         d.Whead = (const uint8_t *)m->head.wd;
         d.x0 = m->h0; d.x1 = m->h1; d.qkv = m->qkv; d.act = m->act; d.logits = m->logits; d.fa_ws = (float *)m->fa_ws; d.part_val = m->part_val;
         d.part_idx = m->part_idx; d.tok_dev = m->tok_dev; d.history = m->history; d.rope_sin = m->dec_sin; d.rope_cos = m->dec_cos; d.cur_sin = m->cur_sin; d.cur_cos = m->cur_cos;
-        d.attn_pairs = m->attn_pairs; d.qkv_pairs = m->qkv_pairs; d.x_pairs = m->x_pairs; d.poll_err = m->poll_err; d.merge_o = option(OPT_MERGE_O) < 0 || option(OPT_MERGE_O) > 4 ? 4 : option(OPT_MERGE_O);      // 4 (default): a layer's down projection + the next layer's q|k|v + attention + o-projection in one launch; 3: q|k|v + attention + o-projection; 2: attention + o-projection; 1: that with two rows per wave; 0: five launches per layer      // 2 (default): one row per wave of the projection role; 1: two (the stand-alone kernel's split)      // default on; option "merge_o" = 0 keeps the two launches      // as it stood when the model was created (the captured graph holds the choice)
+        d.attn_pairs = m->attn_pairs; d.qkv_pairs = m->qkv_pairs; d.x_pairs = m->x_pairs; d.poll_err = m->poll_err;
         d.kslab = m->kslab; d.vslab = m->vslab; d.vt_ld = m->vt_ld; d.n_layers = c.layers; d.normed = m->normed; d.x80_qs = m->x80_qs; d.x80_d = m->x80_d;
         for (auto &L : m->layers) {
             DecodeLayer dl;
@@ -484,13 +485,13 @@ static int create_impl(M *m, const MllmFile &f) {
             dl.Wgu_raw = (const uint8_t *)L.gu.w; dl.Wdown_raw = (const uint8_t *)L.down.w; dl.Wo_raw = (const uint8_t *)L.o.w;
             m->dlayers.push_back(dl);
         }
-        {      // the attention launch's weight-warming regions, one entry per layer (read when the model is created: the captured graph holds the pointer)
+        decode_step_plan(d, m->dlayers.data(), (int)m->dlayers.size(), &m->plan);      // the launch-form options are read here, and only here
+        {      // the attention launch's weight-warming regions, one entry per layer (built when the model is created: the captured graph holds the pointer)
             std::vector<WeightWarm> tab(m->dlayers.size());
-            const int fl = decode_attn_flags();
-            d.attn_flags = fl;
+            const int fl = m->plan.attn_flags;
             d.warm_tab = nullptr;
             // (the o-projection's rows need no warming when its workgroups ride in the attention's launch and fetch them there)
-            if ((fl & 1) && !(fl & 4) && decode_warm_table(d, m->dlayers.data(), (int)m->dlayers.size(), decode_merges_o(d) ? fl & ~64 : fl, tab.data()) > 0) {
+            if ((fl & 1) && !(fl & 4) && decode_warm_table(d, m->dlayers.data(), (int)m->dlayers.size(), m->plan.o_in_attn ? fl & ~64 : fl, tab.data()) > 0) {
                 WeightWarm *dev = nullptr;
                 EH(m->dalloc(&dev, tab.size() * sizeof(WeightWarm)));
                 HH(hipMemcpy(dev, tab.data(), tab.size() * sizeof(WeightWarm), hipMemcpyHostToDevice));
@@ -938,9 +939,9 @@ static int finish(M *m, float *logits_host, int32_t *next_token, float *elapsed_
     // the copies ride the stream behind the step and ONE synchronisation covers the step and both of them
     if (logits_host) HH(hipMemcpyAsync(logits_host, m->logits, (size_t)m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     if (next_token) HH(hipMemcpyAsync(m->pin_tok + 1, m->tok_dev, 4, hipMemcpyDeviceToHost, m->st));
-    if (m->dctx.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, m->st));
+    if (m->plan.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, m->st));
     HH(hipStreamSynchronize(m->st));
-    if (m->dctx.merge_o && *m->pin_err) {      // a polled hand-off inside a merged launch gave up: the results of the step(s) are not valid
+    if (m->plan.merge_o && *m->pin_err) {      // a polled hand-off inside a merged launch gave up: the results of the step(s) are not valid
         const int site = *m->pin_err;
         *m->pin_err = 0;
         HH(hipMemset(m->poll_err, 0, 4));
@@ -1031,7 +1032,8 @@ static int arm_decode(M *m) {
     HH(hipMemcpy(&tok, m->tok_dev, 4, hipMemcpyDeviceToHost));
     DecodeState st0 = {m->cache_len, 0, tok, 0};
     HH(hipMemcpy(m->d_state, &st0, sizeof(st0), hipMemcpyHostToDevice));
-    if (m->dctx.merge_o) { HH(hipMemset(m->attn_pairs, 0xFF, (size_t)m->c.layers * m->HD * 8)); HH(hipMemset(m->qkv_pairs, 0xFF, (size_t)m->c.layers * m->QKV * 8)); HH(hipMemset(m->x_pairs, 0xFF, (size_t)m->c.layers * m->c.hidden * 8)); }      // no pair of an earlier run may carry an epoch this run will count up to      // no pair of an earlier run may carry an epoch this run will count up to
+    // no pair of an earlier run may carry an epoch this run will count up to
+    if (m->plan.merge_o) { HH(hipMemset(m->attn_pairs, 0xFF, (size_t)m->c.layers * m->HD * 8)); HH(hipMemset(m->qkv_pairs, 0xFF, (size_t)m->c.layers * m->QKV * 8)); HH(hipMemset(m->x_pairs, 0xFF, (size_t)m->c.layers * m->c.hidden * 8)); }
     return 0;
 }
 
@@ -1039,7 +1041,7 @@ static int launch_step(M *m) {
     if (m->use_graph) {
         if (!m->graph_exec) {
             HH(hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal));
-            int rc = decode_step_launch(m->dctx, m->dlayers.data(), (int)m->dlayers.size(), m->st);
+            int rc = decode_step_launch(m->dctx, m->plan, m->dlayers.data(), m->st);
             hipError_t e = hipStreamEndCapture(m->st, &m->graph);
             if (rc) return rc;
             HH(e);
@@ -1048,7 +1050,7 @@ static int launch_step(M *m) {
         HH(hipGraphLaunch(m->graph_exec, m->st));
         return 0;
     }
-    return decode_step_launch(m->dctx, m->dlayers.data(), (int)m->dlayers.size(), m->st);
+    return decode_step_launch(m->dctx, m->plan, m->dlayers.data(), m->st);
 }
 
 // After a failure inside a decode loop the host's counters follow the device's DecodeState (which the steps that did run have advanced), so a caller that carries on
@@ -1136,7 +1138,7 @@ extern "C" int mllm_hip_model_time_step(mllm_hip_model *m, int32_t first_token, 
     HH(hipEventRecord(m->ev0, m->st));
     for (int s = 0; s < steps; ++s) {      // all steps are queued before the one synchronisation: after the first step the host runs ahead of the device
         first[s] = t.n;
-        if (int rc = decode_step_launch(m->dctx, m->dlayers.data(), (int)m->dlayers.size(), m->st, &marks)) return resync_after_error(m, rc);
+        if (int rc = decode_step_launch(m->dctx, m->plan, m->dlayers.data(), m->st, &marks)) return resync_after_error(m, rc);
     }
     first[steps] = t.n;
     m->cache_len += steps;
@@ -1418,11 +1420,13 @@ extern "C" int mllm_hip_model_time_kernel(mllm_hip_model *m, int which, int iter
     if (!m || !m->has_llm || iters <= 0) return MLLM_HIP_ERR_ARG;
     int nl = (int)m->layers.size();
     if (option(OPT_TIME_LAYERS) > 0) nl = std::max(1, std::min(nl, option(OPT_TIME_LAYERS)));   // fewer layers: an Infinity-Cache-warm stream
-    DecodeCtx alone = m->dctx;      // the kernels one at a time: the step's merged launch (attention + o-projection) is taken apart
-    alone.merge_o = 0;
     auto launch = [&](int i) -> int {
         auto &L = m->layers[i % nl];
-        if (which >= 10) return decode_kernel_launch(alone, m->dlayers.data(), i % nl == 0 && which == 10 ? 1 % nl : i % nl, which - 10, m->st);
+        if (which > 14) return MLLM_HIP_ERR_ARG;
+        if (which >= 10) {      // the kernels one at a time, whatever the step's plan merged (q|k|v: not layer 0's embedding form)
+            const int li = i % nl == 0 && which == 10 ? 1 % nl : i % nl;
+            return decode_launch(m->dctx, m->plan, m->dlayers.data(), m->plan.alone[5 * li + which - 10], m->st);
+        }
         const LinearW &w = which == 0 ? L.gu : (which == 1 ? L.down : (which == 2 ? L.qkv : L.o));
         const Q8Planes &x = which == 1 ? m->xq2 : m->xq;
         float *y = which == 0 ? m->gu : m->h1;

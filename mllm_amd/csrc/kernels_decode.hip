@@ -1500,7 +1500,7 @@ static int allow_lds(KernelT kern, size_t lds) {
 // RMSNorm(x) -> Q8_K -> W rows (+bias) -> y: the q|k|v projection of a layer, and the Linear lm_head of the models whose head is not tied
 template <int NS>
 static int launch_norm_gemv(const DecodeCtx &c, const float *norm_w, float eps, const uint8_t *W, const float *bias, int N, bool embed, const float *x,
-                            float *x_out, float *y, hipStream_t st, const KvWarm &kw = KvWarm{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0}) {
+                            float *x_out, float *y, int persist, hipStream_t st, const KvWarm &kw = KvWarm{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0}) {
 #ifndef QKV_ROWS
 #define QKV_ROWS 2
 #endif
@@ -1511,10 +1511,7 @@ static int launch_norm_gemv(const DecodeCtx &c, const float *norm_w, float eps, 
     const int waves = (N + ROWS - 1) / ROWS;
     const size_t lds = fused_lds_bytes<NS, ROWS>(c.H, false, WPB);
     constexpr int NV = (NS * 8 + WPB - 1) / WPB;   // quant blocks per wave
-    // long rows (LLaVA-1.5-7B: 12,288 one-row waves = 1,536 workgroups, each with its own RMSNorm + Q8_K of the 4,096-value row): a grid of qkv_persist workgroups per CU walks them
-    // (short rows too when there are at least four times as many workgroups as the walking grid: the untied lm_heads -- TinyLlama 2,000, Qwen1.5 9,496 workgroups)
-    const int persist = option(OPT_QKV_PERSIST) >= 0 ? option(OPT_QKV_PERSIST) : (NS >= 2 || (waves + WPB - 1) / WPB >= 1024 ? 2 : 0);
-    if (!embed && persist > 0 && (waves + WPB - 1) / WPB > 256 * persist) {
+    if (persist > 0) {      // the walking form: `persist` workgroups per CU (the plan's norm_gemv_walk)
         int wrc = allow_lds(dec_qkv_walk_kernel<NS, ROWS, NV, WPB>, lds);
         if (wrc) return wrc;
         hipLaunchKernelGGL((dec_qkv_walk_kernel<NS, ROWS, NV, WPB>), dim3(256 * persist), dim3(64 * WPB), lds, st, c.state, x, x_out, c.emb_qs, c.emb_d, c.vocab, norm_w, eps, W, bias, y,
@@ -1532,7 +1529,7 @@ static int launch_norm_gemv(const DecodeCtx &c, const float *norm_w, float eps, 
     return MH_LAUNCH_OK("dec_qkv");
 }
 template <int NS>
-static int launch_gateup(const DecodeLayer &L, const DecodeCtx &c, const float *x, hipStream_t st) {
+static int launch_gateup(const DecodeLayer &L, const DecodeCtx &c, const float *x, bool gub, int persist, hipStream_t st) {
 #ifndef GU_PAIRS
 #define GU_PAIRS 2
 #endif
@@ -1545,8 +1542,7 @@ static int launch_gateup(const DecodeLayer &L, const DecodeCtx &c, const float *
 #ifndef GUB_WPB
 #define GUB_WPB 7
 #endif
-    const bool gub_off = option(OPT_NO_GUB) > 0;      // bring-up switch: the 8-lanes-per-block kernel instead
-    if (MLLM_HIP_GUB && !gub_off && NS == 1 && 2 * GUB_PAIRS * (c.H >> 8) <= 64 && c.I % GUB_PAIRS == 0 && (c.H >> 8) <= GUB_WPB) {
+    if (gub) {      // one lane per super-block (the plan's gub_serves)
         constexpr int BP = GUB_PAIRS, BW = GUB_WPB, BNV = 1;      // one quant block per wave in the prologue: K/256 <= waves
         const int bw = c.I / BP;
         const size_t blds = gub_lds_bytes(c.H, BP, BW);
@@ -1563,14 +1559,12 @@ static int launch_gateup(const DecodeLayer &L, const DecodeCtx &c, const float *
     int rc = allow_lds(kern, lds);
     if (rc) return rc;
     int grid = (waves + WPB - 1) / WPB;
-    // workgroups per CU of the persistent form (LLaVA-1.5-7B: 1,376 -> 512 workgroups, each walking 2.7 row groups behind one prologue: 19.5 -> 15.2 us; 1 / 3 / 4 per CU: 17.3 - 17.6)
-    const int persist = option(OPT_GU_PERSIST) >= 0 ? option(OPT_GU_PERSIST) : (NS >= 2 ? 2 : 0);
     if (persist > 0) grid = std::min(grid, 256 * persist);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WPB), lds, st, x, L.post_norm, c.eps, L.Wgu, c.act, c.I, c.H);
     return MH_LAUNCH_OK("dec_gateup");
 }
 template <int NS>
-static int launch_proj(const uint8_t *W, const uint8_t *Wraw, const float *xin, const float *residual, float *y, int N, int K, hipStream_t st) {
+static int launch_proj(const uint8_t *W, const uint8_t *Wraw, const float *xin, const float *residual, float *y, int N, int K, bool blk, hipStream_t st) {
 #ifndef PJ_ROWS1
 #define PJ_ROWS1 2
 #endif
@@ -1583,21 +1577,15 @@ static int launch_proj(const uint8_t *W, const uint8_t *Wraw, const float *xin, 
 #ifndef PJ_WPB1
 #define PJ_WPB1 8
 #endif
-    // one lane per super-block: rows per workgroup chosen for one workgroup per CU (256) within the 512 lanes of a workgroup
-    const bool pjb_off = option(OPT_NO_PJB) > 0;
-    const int pjb_min_ns = option(OPT_PJB_MIN_NS) >= 0 ? option(OPT_PJB_MIN_NS) : 3;   // short rows: the 8-lane kernel is faster
-    {
-        const int nb = K >> 8;
+    if (blk) {      // one lane per super-block (the plan's pjb_serves): rows per workgroup chosen for one workgroup per CU (256) within the 512 lanes of a workgroup
+        constexpr int BW = 8, NQ = NS;
         const int rpw = pjb_rows_per_wg(N, K);
-        if (NS >= pjb_min_ns && NS <= 5 && Wraw && !pjb_off && N >= rpw) {
-            constexpr int BW = 8, NQ = NS;
-            const size_t blds = pjb_lds_bytes(K, rpw);
-            auto bk = dec_proj_blk_kernel<BW, NQ>;
-            int brc = allow_lds(bk, blds);
-            if (brc) return brc;
-            hipLaunchKernelGGL(bk, dim3((N + rpw - 1) / rpw), dim3(64 * BW), blds, st, xin, Wraw, residual, y, N, K, rpw);
-            return MH_LAUNCH_OK("dec_proj_blk");
-        }
+        const size_t blds = pjb_lds_bytes(K, rpw);
+        auto bk = dec_proj_blk_kernel<BW, NQ>;
+        int brc = allow_lds(bk, blds);
+        if (brc) return brc;
+        hipLaunchKernelGGL(bk, dim3((N + rpw - 1) / rpw), dim3(64 * BW), blds, st, xin, Wraw, residual, y, N, K, rpw);
+        return MH_LAUNCH_OK("dec_proj_blk");
     }
     constexpr int ROWS = NS == 1 ? PJ_ROWS1 : PJ_ROWS5, WPB = NS >= 3 ? PJ_WPB5 : PJ_WPB1;   // long rows: 1024-thread workgroups share the row quantisation
     const int waves = (N + ROWS - 1) / ROWS;
@@ -1809,7 +1797,8 @@ int row_fused_launch(const RowFusedArgs &in, hipStream_t st) {
     const int total = row_fused_plan(A);
     if (total <= 0) return total ? total : MLLM_HIP_ERR_SHAPE;
     const int K = A.K, nsr = (K / 256 + 7) / 8;
-    // the MLP's run on the 2 B model's shape: the engine's own gate|up kernel (a wave per five row pairs, no workgroup barrier behind the prologue) with the Ops' outputs added
+    // the MLP's run on the 2 B model's shape: the engine's own gate|up kernel (a wave per five row pairs, no workgroup barrier behind the prologue) with the Ops' outputs added.
+    // The shape test is gub_serves' (the decode step's plan) with GUB_PAIRS = 5, GUB_WPB = 7 written out; option no_gub is read here at every call: the adapter has no model
     if (A.mode == 1 && option(OPT_NO_GUB) <= 0 && 2 * 5 * (K >> 8) <= 64 && (K >> 8) <= 7 && A.seg[0].N % 5 == 0 && !A.seg[0].bias && !A.seg[1].bias && A.norm_w) {
         constexpr int BP = 5, BW = 7;
         const int I = A.seg[0].N, bw = I / BP;
@@ -1845,7 +1834,6 @@ int row_fused_launch(const RowFusedArgs &in, hipStream_t st) {
     default: return MLLM_HIP_ERR_SHAPE;                \
     }
 
-// one fused kernel of layer `li`: 0 qkv, 1 attn, 2 o-proj, 3 gate|up, 4 down. x = layer input / output, t = post-attention residual
 // raw Q4_K rows -> decode order (one thread per dword of the nibble area; headers copied)
 __global__ void q4k_decode_order_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int64_t n_blocks) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // dword index over n_blocks * 36
@@ -1863,9 +1851,6 @@ int decode_order_q4k(const void *src, void *dst, int64_t n_blocks, hipStream_t s
     return MH_LAUNCH_OK("q4k_decode_order");
 }
 
-// the attention flags in force (option "attn_flags", else the default): bit 0 XCD placement of a K/V group's heads, bit 1 two-stage key fetch (un-pipelined kernel),
-// bit 2 keep the un-pipelined kernel, bit 3 dec_qkv warms the L2 with the cache rows, bits 4..7 weight-warming workgroups (decode_warm_table)
-int decode_attn_flags() { return option(OPT_ATTN_FLAGS) >= 0 ? option(OPT_ATTN_FLAGS) : 91; }
 // the table of warming regions of every layer (host side; the engine uploads it once): which rows the launches behind layer li's attention will stream, and how they
 // fall onto those launches' workgroups.  flags = the attention flags: bit 4 gate|up, bit 5 down, bit 6 o-projection, bit 7 the next layer's q|k|v.  Returns 0 when no layer has
 // a region (the caller then leaves DecodeCtx::warm_tab null).
@@ -1900,189 +1885,179 @@ int decode_warm_table(const DecodeCtx &c, const DecodeLayer *layers, int n_layer
     return any;
 }
 
-// whether case 1 of decode_kernel_launch carries the o-projection (the same conditions as there)
-template <int D>
-static size_t merged_o_lds(const DecodeCtx &c) {
-    constexpr int NP_ = DEC_PIPE_NT / 64 - ((D / 2 + 63) / 64) - 1;
-    return std::max(pipe_lds_bytes<D, D / 2>(c.cache_limit, NP_), fused_lds_bytes<1, 2>(c.heads * c.D, false, 8));
+// ---- the step plan (decode_launch.h): every launch-form option is read here, once, when the model is created ---------------------------------------------------------------
+// the options as decode_step_plan read them (o_in_attn: merges_o's answer, asked once)
+struct StepOptions { int merge_o, attn_flags, attn_ds, chain_cont, pjb_min_ns, no_pjb, no_gub, gu_persist, qkv_persist, head_wpc; bool o_in_attn; };
+// dynamic LDS of the pipelined attention on D-wide heads split over ds workgroups (dec_attn_pipe_kernel<D, ds>; ds = 2 is also the attention role of the shared launches)
+static size_t attn_pipe_lds(int D, int ds, int cache_limit) {
+#define PIPE_LDS(DD, DSV) pipe_lds_bytes<DD, DD / DSV>(cache_limit, DEC_PIPE_NT / 64 - ((DD / DSV + 63) / 64) - 1)
+    if (D == 128) return ds == 1 ? PIPE_LDS(128, 1) : (ds == 2 ? PIPE_LDS(128, 2) : PIPE_LDS(128, 4));
+    return ds == 1 ? PIPE_LDS(64, 1) : (ds == 2 ? PIPE_LDS(64, 2) : PIPE_LDS(64, 4));
+#undef PIPE_LDS
 }
-bool decode_merges_o(const DecodeCtx &c) {
-    if (!c.merge_o || !c.attn_pairs || (c.attn_flags & 4) || c.cache_limit > 2048 || (c.D != 128 && c.D != 64)) return false;
-    const int ds_env = option(OPT_ATTN_DS) > 0 ? option(OPT_ATTN_DS) : 0;
-    if (!(ds_env == 0 || ds_env == 2)) return false;
-    if ((c.heads * c.D) > 2048 || (c.heads * c.D) % 256) return false;      // the projection's register form (dec_proj_kernel<1, ..>: rows of at most eight super-blocks)
-    return (c.D == 128 ? merged_o_lds<128>(c) : merged_o_lds<64>(c)) <= (size_t)(160 * 1024 - 2 * c.D * 2 - 64);
+// workgroups of the roles of the shared launches (eight-wave workgroups; q|k|v: two rows per wave)
+static int qkv_role_grid(int qkv_N) { return ((qkv_N + 1) / 2 + 7) / 8; }
+static int oproj_role_grid(int N, int rows) { return ((N + rows - 1) / rows + 7) / 8; }
+// the lane-per-super-block projection (dec_proj_blk) serves y[N] = W[N][K] x: rows of 17 .. 40 super-blocks by default (shorter rows: the eight-lane kernel is faster)
+static bool pjb_serves(const StepOptions &p, const uint8_t *Wraw, int N, int K) {
+    const int NS = (K / 256 + 7) / 8;
+    return K >= 256 && NS >= p.pjb_min_ns && NS <= 5 && Wraw && !p.no_pjb && N >= pjb_rows_per_wg(N, K);
 }
-// ... and the q|k|v projection in front of it (merge_o = 3): hidden sizes the projection's register form covers, a q|k|v grid that keeps the XCD columns of the launch
-template <int D>
-static size_t merged_front_lds(const DecodeCtx &c) { return std::max(merged_o_lds<D>(c), fused_lds_bytes<1, 2>(c.H, false, 8)); }
-static bool decode_merges_front(const DecodeCtx &c, const DecodeLayer &L, int li) {
-    // (not layer 0: its q|k|v role also writes the embedding row that the o-projection adds back -- a plain store another workgroup of the same launch would read)
-    if (li == 0 || c.merge_o < 3 || !c.qkv_pairs || !decode_merges_o(c) || c.H > 2048 || c.H % 256) return false;
-    const int grid_q = ((L.qkv_N + 1) / 2 + 7) / 8;
-    if (grid_q & 7) return false;
-    return (c.D == 128 ? merged_front_lds<128>(c) : merged_front_lds<64>(c)) <= (size_t)(160 * 1024 - 2 * c.D * 2 - 64);
+// the lane-per-super-block gate|up (dec_gateup_blk); option no_gub is the bring-up switch back to the eight-lanes-per-block kernel
+static bool gub_serves(const StepOptions &p, const DecodeCtx &c) {
+    return MLLM_HIP_GUB && !p.no_gub && (c.H / 256 + 7) / 8 == 1 && 2 * GUB_PAIRS * (c.H >> 8) <= 64 && c.I % GUB_PAIRS == 0 && (c.H >> 8) <= GUB_WPB;
 }
-// ... and the previous layer's down projection in front of those (merge_o = 4): layer li's down projection carries layer li + 1's q|k|v + attention + o-projection
-template <int D>
-static size_t merged_chain_lds(const DecodeCtx &c) { return std::max(merged_front_lds<D>(c), pjb_lds_bytes(c.I, pjb_rows_per_wg(c.H, c.I))); }
-static bool decode_merges_chain(const DecodeCtx &c, const DecodeLayer *layers, int li) {
-    if (c.merge_o < 4 || !c.x_pairs || li < 0 || li + 1 >= c.n_layers || c.I % 256) return false;
-    DecodeCtx f = c;
-    f.merge_o = 3;
-    if (!decode_merges_front(f, layers[li + 1], li + 1)) return false;
-    const int NS = (c.I / 256 + 7) / 8, rpw = pjb_rows_per_wg(c.H, c.I), grid_d = (c.H + rpw - 1) / rpw;
-    const int pjb_min_ns = option(OPT_PJB_MIN_NS) >= 0 ? option(OPT_PJB_MIN_NS) : 3;
-    if (!(NS >= pjb_min_ns && NS <= 5 && layers[li].Wdown_raw && option(OPT_NO_PJB) <= 0 && c.H >= rpw) || (grid_d & 7)) return false;
-    return (c.D == 128 ? merged_chain_lds<128>(c) : merged_chain_lds<64>(c)) <= (size_t)(160 * 1024 - 2 * c.D * 2 - 64);
+// workgroups per CU of launch_norm_gemv's walking form, 0 = a workgroup per row group.  Long rows (LLaVA-1.5-7B: 12,288 one-row waves = 1,536 workgroups, each with its own
+// RMSNorm + Q8_K of the 4,096-value row) are walked, and short rows too when there are at least four times as many workgroups as the walking grid (the untied lm_heads:
+// TinyLlama 2,000, Qwen1.5 9,496 workgroups)
+static int norm_gemv_walk(const StepOptions &p, int K, int N, bool embed) {
+    const int NS = (K / 256 + 7) / 8, rows = NS == 1 ? QKV_ROWS : 1, wgs = ((N + rows - 1) / rows + QKV_WPB - 1) / QKV_WPB;
+    const int persist = p.qkv_persist >= 0 ? p.qkv_persist : (NS >= 2 || wgs >= 1024 ? 2 : 0);
+    return !embed && persist > 0 && wgs > 256 * persist ? persist : 0;
 }
-int decode_kernel_launch(const DecodeCtx &c, const DecodeLayer *layers, int li, int which, hipStream_t st) {
-    if ((c.D != 128 && c.D != 64) || c.heads % c.kv_heads) return MLLM_HIP_ERR_SHAPE;
-    float *x = c.x0, *t = c.x1;
-    const DecodeLayer &L = layers[li];
-    int rc = 0;
-    switch (which) {
-    case 0:
-    {
-        if (decode_merges_chain(c, layers, li - 1)) return MLLM_HIP_OK;      // this layer's q|k|v + attention + o-projection rode in the previous layer's down-projection launch
-        if (decode_merges_front(c, L, li)) {
-            uint16_t *kl = c.kslab + (size_t)li * c.cache_limit * c.kv_heads * c.D, *vl = c.vslab + (size_t)li * c.kv_heads * c.D * c.vt_ld;
-            const int flags = c.attn_flags, ds = 2;
-            const int grid_a0 = (flags & 1) ? dec_attn_grid(c.heads, c.kv_heads, ds) : c.heads * ds, attn_groups = grid_a0 / 8;
-            const WeightWarm *ww = (flags & 1) && !(flags & 4) && c.warm_tab ? c.warm_tab + li : nullptr;
-            const int grid_attn = grid_a0 + (ww ? 8 * std::max(8, WeightWarm::GROUPS - attn_groups) : 0);      // the attention's workgroups and, behind them, the warming ones
-            const int grid_q = ((L.qkv_N + 1) / 2 + 7) / 8;
-            const int rows = 1, Ko = c.heads * c.D, grid_o = ((c.H + rows - 1) / rows + 7) / 8;
-            KvWarm kw{nullptr, nullptr, nullptr, c.kv_heads, c.D, c.kv_heads * c.D, c.vt_ld, c.cache_limit};
-            if ((flags & 8) && (flags & 1) && c.kv_heads <= 8) { kw.kslab = kl; kw.vslab = vl; }
-            const QkvFront F{x, x, c.emb_qs, c.emb_d, L.in_norm, L.Wqkv, L.bqkv, c.qkv_pairs + (size_t)li * L.qkv_N, c.eps, c.vocab, L.qkv_N, c.H, grid_q, kw};
-            const OProjRole P{L.Wo, x, t, c.attn_pairs + (size_t)li * Ko, c.poll_err, c.H, Ko, grid_attn, rows};
-            const size_t plds = c.D == 128 ? merged_front_lds<128>(c) : merged_front_lds<64>(c);
-#define FRONT_CASE(DD, EMB)                                                                                                                                   \
-    {                                                                                                                                                         \
-        rc = allow_lds(dec_qkv_attn_oproj_kernel<DD, 2, EMB>, plds);                                                                                          \
-        if (rc) return rc;                                                                                                                                    \
-        hipLaunchKernelGGL((dec_qkv_attn_oproj_kernel<DD, 2, EMB>), dim3(grid_q + grid_attn + grid_o), dim3(DEC_PIPE_NT), plds, st, c.state, c.cur_sin, c.cur_cos, kl, vl, c.heads, \
-                           c.kv_heads, c.cache_limit, c.vt_ld, flags, attn_groups, ww, F, P);                                                                 \
-    }
-            if (c.D == 128) FRONT_CASE(128, false) else FRONT_CASE(64, false)
-#undef FRONT_CASE
-            return MH_LAUNCH_OK("dec_qkv_attn_oproj");
-        }
-        // bit 3 of the attention flags (set by default): dec_qkv warms the L2 with the layer's cache rows for the attention launch that follows
-        const int aflags = c.attn_flags;
-        KvWarm kw{nullptr, nullptr, nullptr, c.kv_heads, c.D, c.kv_heads * c.D, c.vt_ld, c.cache_limit};
-        if ((aflags & 8) && (aflags & 1) && c.kv_heads <= 8) {
-            kw.kslab = c.kslab + (size_t)li * c.cache_limit * c.kv_heads * c.D;
-            kw.vslab = c.vslab + (size_t)li * c.kv_heads * c.D * c.vt_ld;
-        }
-        NS_DISPATCH(c.H, rc = launch_norm_gemv<NS>(c, L.in_norm, c.eps, L.Wqkv, L.bqkv, L.qkv_N, li == 0, x, x, c.qkv, st, kw));
-        return rc;
-    }
-    case 1: {
-        if (decode_merges_chain(c, layers, li - 1) || decode_merges_front(c, L, li)) return MLLM_HIP_OK;      // done inside the q|k|v launch (or the previous down-projection's)
-        uint16_t *kl = c.kslab + (size_t)li * c.cache_limit * c.kv_heads * c.D, *vl = c.vslab + (size_t)li * c.kv_heads * c.D * c.vt_ld;
-        const int nslots = decode_lds_slots(c.cache_limit, c.D, DEC_ATTN_NT, 2, true);
-        const size_t lds = decode_lds_bytes(c.cache_limit, c.D, DEC_ATTN_NT, 2, nslots, true);
-        // bit 0: XCD placement of a K/V group's heads, bit 1: two-stage key fetch (both neutral in time at T = 290..430, profiles/r02_attn_experiments.md;
-        // the second keeps the fetched bytes near the algorithmic ones at short contexts)
-        const int flags = c.attn_flags;
-        const int ds_env = option(OPT_ATTN_DS) > 0 ? option(OPT_ATTN_DS) : 0;     // workgroups per head (1, 2 or 4); 0 = default
-        const int ds = ds_env == 1 || ds_env == 2 || ds_env == 4 ? ds_env : 2;
-        const dim3 grid((flags & 1) ? dec_attn_grid(c.heads, c.kv_heads, ds) : c.heads * ds);
-        // the workgroups the attention does not need read this layer's gate|up (and o-projection) rows, so that the XCD L2s hold them when those launches arrive
-        const int attn_groups = (int)grid.x / 8;
-        const WeightWarm *ww = (flags & 1) && !(flags & 4) && c.warm_tab ? c.warm_tab + li : nullptr;
+// dynamic LDS of the three shared launches: the largest of their roles'
+static size_t merged_o_lds(const DecodeCtx &c) { return std::max(attn_pipe_lds(c.D, 2, c.cache_limit), fused_lds_bytes<1, 2>(c.heads * c.D, false, 8)); }
+static size_t merged_front_lds(const DecodeCtx &c) { return std::max(merged_o_lds(c), fused_lds_bytes<1, 2>(c.H, false, 8)); }
+static size_t merged_chain_lds(const DecodeCtx &c) { return std::max(merged_front_lds(c), pjb_lds_bytes(c.I, pjb_rows_per_wg(c.H, c.I))); }
+static bool shared_lds_fits(const DecodeCtx &c, size_t lds) { return lds <= (size_t)(160 * 1024 - 2 * c.D * 2 - 64); }
+// the o-projection rides in the attention's launch (merge_o >= 1): the pipelined attention on two workgroups per head, and a projection its register form covers
+// (dec_proj_kernel<1, ..>: rows of at most eight super-blocks)
+static bool merges_o(const StepOptions &p, const DecodeCtx &c) {
+    if (!p.merge_o || !c.attn_pairs || (p.attn_flags & 4) || c.cache_limit > 2048 || (c.D != 128 && c.D != 64) || !(p.attn_ds == 0 || p.attn_ds == 2)) return false;
+    return (c.heads * c.D) <= 2048 && (c.heads * c.D) % 256 == 0 && shared_lds_fits(c, merged_o_lds(c));
+}
+// ... and the q|k|v projection in front of it (merge_o >= 3): hidden sizes the projection's register form covers, a q|k|v grid that keeps the XCD columns of the launch.
+// Not layer 0: its q|k|v role also writes the embedding row that the o-projection adds back -- a plain store another workgroup of the same launch would read.
+static bool merges_front(const StepOptions &p, const DecodeCtx &c, const DecodeLayer *layers, int li) {
+    if (li == 0 || p.merge_o < 3 || !c.qkv_pairs || !p.o_in_attn || c.H > 2048 || c.H % 256) return false;
+    return !(qkv_role_grid(layers[li].qkv_N) & 7) && shared_lds_fits(c, merged_front_lds(c));
+}
+// ... and the previous layer's down projection in front of those (merge_o = 4): layer li's down projection (dec_proj_blk's body, a grid that keeps the XCD columns) carries
+// layer li + 1's q|k|v + attention + o-projection
+static bool merges_chain(const StepOptions &p, const DecodeCtx &c, const DecodeLayer *layers, int li) {
+    if (p.merge_o < 4 || !c.x_pairs || li < 0 || li + 1 >= c.n_layers || c.I % 256 || !merges_front(p, c, layers, li + 1)) return false;
+    if (!pjb_serves(p, layers[li].Wdown_raw, c.H, c.I)) return false;
+    const int rpw = pjb_rows_per_wg(c.H, c.I), grid_d = (c.H + rpw - 1) / rpw;
+    return !(grid_d & 7) && shared_lds_fits(c, merged_chain_lds(c));
+}
+// kernel `kind` (STEP_QKV .. STEP_DOWN) of layer li as a launch of its own
+static StepLaunch unmerged_launch(const StepOptions &p, const DecodeCtx &c, const DecodeLayer *layers, int li, int kind) {
+    StepLaunch e{};
+    e.kind = kind;
+    e.layer = li;
+    switch (kind) {
+    case STEP_QKV: e.persist = norm_gemv_walk(p, c.H, layers[li].qkv_N, li == 0); break;
+    case STEP_ATTN:
+        e.ds = p.attn_ds == 1 || p.attn_ds == 2 || p.attn_ds == 4 ? p.attn_ds : 2;
         // bit 2 of the flags (unset by default) keeps the un-pipelined kernel; caches beyond 2048 keys (more than 64 blocks: the carry is taken by one wave pass) stay on it too
-        // option "merge_o": the o-projection rides in the attention's launch (K <= 2048: the register form dec_proj_kernel<1, 2, 8>); case 2 below is then a no-op
-        if (decode_merges_o(c)) {
-            const size_t plds = c.D == 128 ? merged_o_lds<128>(c) : merged_o_lds<64>(c);
-            const int grid_attn = (int)grid.x + (ww ? 8 * std::max(8, WeightWarm::GROUPS - attn_groups) : 0);
-            const int rows = c.merge_o == 2 ? 1 : 2;      // rows per wave of the projection role (1: twice the workgroups, on CUs the attention leaves idle anyway)
-            const int K = c.heads * c.D, waves = (c.H + rows - 1) / rows;
-            const OProjRole P{L.Wo, x, t, c.attn_pairs + (size_t)li * K, c.poll_err, c.H, K, grid_attn, rows};
-#define MERGED_O_CASE(DD)                                                                                                                                      \
-    {                                                                                                                                                         \
-        rc = allow_lds(dec_attn_oproj_kernel<DD, 2>, plds);                                                                                                   \
-        if (rc) return rc;                                                                                                                                    \
-        hipLaunchKernelGGL((dec_attn_oproj_kernel<DD, 2>), dim3(grid_attn + (waves + 7) / 8), dim3(DEC_PIPE_NT), plds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, kl, vl, c.heads, \
-                           c.kv_heads, c.cache_limit, c.vt_ld, flags, attn_groups, ww, P);                                                                    \
-    }
-            if (c.D == 128) MERGED_O_CASE(128) else MERGED_O_CASE(64)
-#undef MERGED_O_CASE
-            return MH_LAUNCH_OK("dec_attn_oproj");
+        if (!(p.attn_flags & 4) && c.cache_limit <= 2048 && (c.D == 128 || c.D == 64)) {
+            e.lds = attn_pipe_lds(c.D, e.ds, c.cache_limit);
+            e.pipe = e.lds <= (size_t)(160 * 1024 - 2 * c.D * 2 - 64);
         }
-        if (!(flags & 4) && c.cache_limit <= 2048 && (c.D == 128 || c.D == 64)) {
-#define DEC_PIPE_CASE(DD, DSV)                                                                                                                            \
-    {                                                                                                                                                     \
-        constexpr int NP_ = DEC_PIPE_NT / 64 - ((DD / DSV + 63) / 64) - 1;                                                                                \
-        const size_t plds = pipe_lds_bytes<DD, DD / DSV>(c.cache_limit, NP_);                                                                             \
-        if (plds <= 160 * 1024 - 2 * DD * 2 - 64) {                                                                                                       \
-            rc = allow_lds(dec_attn_pipe_kernel<DD, DSV>, plds);                                                                                          \
-            if (rc) return rc;                                                                                                                            \
-            hipLaunchKernelGGL((dec_attn_pipe_kernel<DD, DSV>), dim3(grid.x + (ww ? 8 * std::max(8, WeightWarm::GROUPS - attn_groups) : 0)), dim3(DEC_PIPE_NT), plds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, kl, vl, c.fa_ws, \
-                               c.heads, c.kv_heads, c.cache_limit, c.vt_ld, flags, attn_groups, ww);                                                      \
-            return MH_LAUNCH_OK("dec_attn_pipe");                                                                                                         \
-        }                                                                                                                                                 \
+        break;
+    case STEP_OPROJ: e.blk = pjb_serves(p, layers[li].Wo_raw, c.H, c.heads * c.D); break;
+    case STEP_GATEUP:
+        e.blk = gub_serves(p, c);
+        // workgroups per CU of the persistent form (LLaVA-1.5-7B: 1,376 -> 512 workgroups, each walking 2.7 row groups behind one prologue: 19.5 -> 15.2 us; 1 / 3 / 4 per CU: 17.3 - 17.6)
+        e.persist = p.gu_persist >= 0 ? p.gu_persist : ((c.H / 256 + 7) / 8 >= 2 ? 2 : 0);
+        break;
+    case STEP_DOWN: e.blk = pjb_serves(p, layers[li].Wdown_raw, c.H, c.I); break;
     }
-            if (c.D == 128) { if (ds == 1) DEC_PIPE_CASE(128, 1) else if (ds == 2) DEC_PIPE_CASE(128, 2) else DEC_PIPE_CASE(128, 4) }
-            else { if (ds == 1) DEC_PIPE_CASE(64, 1) else if (ds == 2) DEC_PIPE_CASE(64, 2) else DEC_PIPE_CASE(64, 4) }
-#undef DEC_PIPE_CASE
+    return e;
+}
+void decode_step_plan(const DecodeCtx &c, const DecodeLayer *layers, int n_layers, StepPlan *out) {
+    StepOptions p;
+    p.merge_o = option(OPT_MERGE_O) < 0 || option(OPT_MERGE_O) > 4 ? 4 : option(OPT_MERGE_O);
+    p.attn_flags = option(OPT_ATTN_FLAGS) >= 0 ? option(OPT_ATTN_FLAGS) : 91;
+    p.attn_ds = option(OPT_ATTN_DS) > 0 ? option(OPT_ATTN_DS) : 0;
+    p.chain_cont = option(OPT_CHAIN_CONT) != 0;
+    p.pjb_min_ns = option(OPT_PJB_MIN_NS) >= 0 ? option(OPT_PJB_MIN_NS) : 3;
+    p.no_pjb = option(OPT_NO_PJB) > 0;
+    p.no_gub = option(OPT_NO_GUB) > 0;
+    p.gu_persist = option(OPT_GU_PERSIST);
+    p.qkv_persist = option(OPT_QKV_PERSIST);
+    p.head_wpc = option(OPT_HEAD_WPC) > 0 ? option(OPT_HEAD_WPC) : 8;
+    p.o_in_attn = merges_o(p, c);
+    StepPlan &plan = *out;
+    plan.merge_o = p.merge_o; plan.attn_flags = p.attn_flags; plan.o_in_attn = p.o_in_attn;
+    plan.launches.clear();
+    plan.alone.resize((size_t)5 * n_layers);
+    for (int i = 0; i < 5 * n_layers; ++i) plan.alone[i] = unmerged_launch(p, c, layers, i / 5, i % 5);
+    auto shared = [](int kind, int li, size_t lds) { StepLaunch e{}; e.kind = kind; e.layer = li; e.ds = 2; e.o_rows = 1; e.lds = lds; return e; };
+    // Rows per wave of the o-projection role, kept as measured: 1 in the front and chain launches (twice the workgroups, on CUs the attention leaves idle anyway) and under
+    // merge_o = 2; 2 in the attention + o-projection launch otherwise -- so under the default merge_o = 4 layer 0 (never in a front / chain launch) runs the two-row form and
+    // layers 1.. the one-row form
+    bool chained = false;      // this layer's q|k|v + attention + o-projection ride in the previous layer's chain launch
+    for (int li = 0; li < n_layers; ++li) {
+        const StepLaunch *alone = &plan.alone[5 * li];
+        if (!chained && merges_front(p, c, layers, li)) plan.launches.push_back(shared(STEP_FRONT, li, merged_front_lds(c)));
+        else if (!chained) {
+            plan.launches.push_back(alone[STEP_QKV]);
+            StepLaunch a = alone[STEP_ATTN];
+            if (p.o_in_attn) { a.o_rows = p.merge_o == 2 ? 1 : 2; a.lds = merged_o_lds(c); }
+            plan.launches.push_back(a);
+            if (!p.o_in_attn) plan.launches.push_back(alone[STEP_OPROJ]);
         }
-#define DEC_ATTN_CASE(DD, DSV)                                                                                                                          \
-    {                                                                                                                                                   \
-        rc = allow_lds(dec_attn_kernel<DD, DSV>, lds);                                                                                                  \
-        if (rc) return rc;                                                                                                                              \
-        hipLaunchKernelGGL((dec_attn_kernel<DD, DSV>), grid, dim3(DEC_ATTN_NT), lds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, kl, vl, c.fa_ws, c.heads, \
-                           c.kv_heads, c.cache_limit, c.vt_ld, nslots, flags);                                                                          \
+        plan.launches.push_back(alone[STEP_GATEUP]);
+        chained = merges_chain(p, c, layers, li);
+        if (chained) {
+            StepLaunch e = shared(STEP_CHAIN, li, merged_chain_lds(c));
+            const int rpw = pjb_rows_per_wg(c.H, c.I);
+            // the q|k|v role runs in the first down-projection workgroups once they are through (+1 %)
+            e.cont = qkv_role_grid(layers[li + 1].qkv_N) <= (c.H + rpw - 1) / rpw && p.chain_cont;
+            plan.launches.push_back(e);
+        } else plan.launches.push_back(alone[STEP_DOWN]);
     }
-        if (c.D == 128) { if (ds == 1) DEC_ATTN_CASE(128, 1) else if (ds == 2) DEC_ATTN_CASE(128, 2) else DEC_ATTN_CASE(128, 4) }
-        else { if (ds == 1) DEC_ATTN_CASE(64, 1) else if (ds == 2) DEC_ATTN_CASE(64, 2) else DEC_ATTN_CASE(64, 4) }
-#undef DEC_ATTN_CASE
-        return MH_LAUNCH_OK("dec_attn");
+    StepLaunch head{}, next{};
+    head.kind = STEP_HEAD;
+    next.kind = STEP_NEXT;
+    if (c.Whead) head.persist = norm_gemv_walk(p, c.H, c.vocab, false);      // Linear lm_head (LLaMA-style models): the q|k|v projection's kernel
+    else if (c.H % 512 != 0 || c.H / 512 > 8) head.head = 1;                  // tied head on shapes the fused head kernel does not cover: the stand-alone launchers
+    else {                                                                    // tied head + partial argmax in one kernel, the rows split for head_wpc waves per CU
+        head.head = 2;
+        head.rows = ((c.vocab + 256 * p.head_wpc - 1) / (256 * p.head_wpc) + 7) / 8 * 8;
+        head.parts = next.parts = ((c.vocab + head.rows - 1) / head.rows + 3) / 4;
     }
-    case 2:
-        if (decode_merges_o(c)) return MLLM_HIP_OK;      // done inside the attention's launch 
-        NS_DISPATCH(c.heads * c.D, rc = (launch_proj<NS>(L.Wo, L.Wo_raw, c.fa_ws, x, t, c.H, c.heads * c.D, st)));
-        return rc;
-    case 3:
-        NS_DISPATCH(c.H, rc = launch_gateup<NS>(L, c, t, st));
-        return rc;
-    case 4:
-        if (decode_merges_chain(c, layers, li)) {
-            const int ln = li + 1;
-            const DecodeLayer &Ln = layers[ln];
-            uint16_t *kl = c.kslab + (size_t)ln * c.cache_limit * c.kv_heads * c.D, *vl = c.vslab + (size_t)ln * c.kv_heads * c.D * c.vt_ld;
-            const int flags = c.attn_flags, ds = 2;
-            const int grid_a0 = (flags & 1) ? dec_attn_grid(c.heads, c.kv_heads, ds) : c.heads * ds, attn_groups = grid_a0 / 8;
-            const WeightWarm *ww = (flags & 1) && !(flags & 4) && c.warm_tab ? c.warm_tab + ln : nullptr;
-            const int grid_attn = grid_a0 + (ww ? 8 * std::max(8, WeightWarm::GROUPS - attn_groups) : 0);
-            const int grid_q = ((Ln.qkv_N + 1) / 2 + 7) / 8, rows = 1, Ko = c.heads * c.D, grid_o = ((c.H + rows - 1) / rows + 7) / 8;
-            const int rpw = pjb_rows_per_wg(c.H, c.I), grid_d = (c.H + rpw - 1) / rpw;
-            KvWarm kw{nullptr, nullptr, nullptr, c.kv_heads, c.D, c.kv_heads * c.D, c.vt_ld, c.cache_limit};
-            if ((flags & 8) && (flags & 1) && c.kv_heads <= 8) { kw.kslab = kl; kw.vslab = vl; }
-            const int cont = grid_q <= grid_d && option(OPT_CHAIN_CONT) != 0;      // the q|k|v role runs in the first down-projection workgroups once they are through (+1 %)
-            const DownRole Dn{c.act, L.Wdown_raw, t, x, c.x_pairs + (size_t)li * c.H, c.H, c.I, rpw, grid_d, cont};
-            const QkvFront F{nullptr, nullptr, c.emb_qs, c.emb_d, Ln.in_norm, Ln.Wqkv, Ln.bqkv, c.qkv_pairs + (size_t)ln * Ln.qkv_N, c.eps, c.vocab, Ln.qkv_N, c.H, grid_q, kw};
-            const OProjRole P{Ln.Wo, nullptr, t, c.attn_pairs + (size_t)ln * Ko, c.poll_err, c.H, Ko, grid_attn, rows};
-            const size_t plds = c.D == 128 ? merged_chain_lds<128>(c) : merged_chain_lds<64>(c);
-#define CHAIN_CASE(DD, NSV)                                                                                                                                   \
-    {                                                                                                                                                         \
-        rc = allow_lds(dec_down_front_kernel<DD, 2, NSV>, plds);                                                                                              \
-        if (rc) return rc;                                                                                                                                    \
-        hipLaunchKernelGGL((dec_down_front_kernel<DD, 2, NSV>), dim3(grid_d + (cont ? 0 : grid_q) + grid_attn + grid_o), dim3(DEC_PIPE_NT), plds, st, c.state, c.cur_sin, c.cur_cos, kl, vl,      \
-                           c.heads, c.kv_heads, c.cache_limit, c.vt_ld, flags, attn_groups, ww, Dn, F, P);                                                    \
+    plan.launches.push_back(head);
+    plan.launches.push_back(next);
+}
+
+// ---- the roles of the shared launches, built in one place each --------------------------------------------------------------------------------------------------------------
+// bit 3 of the attention flags (set by default): the q|k|v projection warms the L2 with the layer's cache rows for the attention that follows
+static KvWarm kv_warm(const DecodeCtx &c, int flags, int li) {
+    KvWarm kw{nullptr, nullptr, nullptr, c.kv_heads, c.D, c.kv_heads * c.D, c.vt_ld, c.cache_limit};
+    if ((flags & 8) && (flags & 1) && c.kv_heads <= 8) {
+        kw.kslab = c.kslab + (size_t)li * c.cache_limit * c.kv_heads * c.D;
+        kw.vslab = c.vslab + (size_t)li * c.kv_heads * c.D * c.vt_ld;
     }
-            const int NSd = (c.I / 256 + 7) / 8;
-            if (c.D == 128) { if (NSd == 3) CHAIN_CASE(128, 3) else if (NSd == 4) CHAIN_CASE(128, 4) else CHAIN_CASE(128, 5) }
-            else { if (NSd == 3) CHAIN_CASE(64, 3) else if (NSd == 4) CHAIN_CASE(64, 4) else CHAIN_CASE(64, 5) }
-#undef CHAIN_CASE
-            return MH_LAUNCH_OK("dec_down_front");
-        }
-        NS_DISPATCH(c.I, rc = (launch_proj<NS>(L.Wdown, L.Wdown_raw, c.act, t, x, c.H, c.I, st)));
-        return rc;
-    }
-    return MLLM_HIP_ERR_ARG;
+    return kw;
+}
+// the attention of layer li on ds workgroups per head: its cache slabs, its workgroups (heads) and, behind them, the warming ones (grid).  Flag bit 0: XCD placement of a
+// K/V group's heads, bit 1: two-stage key fetch (both neutral in time at T = 290..430, profiles/r02_attn_experiments.md; the second keeps the fetched bytes near the
+// algorithmic ones at short contexts).  The workgroups the attention does not need read the rows of the launches behind it (decode_warm_table) into the XCD L2s.
+struct AttnRole { uint16_t *kl, *vl; const WeightWarm *ww; int heads, groups, grid; };
+static AttnRole attn_role(const DecodeCtx &c, int flags, int li, int ds) {
+    AttnRole a;
+    a.kl = c.kslab + (size_t)li * c.cache_limit * c.kv_heads * c.D;
+    a.vl = c.vslab + (size_t)li * c.kv_heads * c.D * c.vt_ld;
+    a.heads = (flags & 1) ? dec_attn_grid(c.heads, c.kv_heads, ds) : c.heads * ds;
+    a.groups = a.heads / 8;
+    a.ww = (flags & 1) && !(flags & 4) && c.warm_tab ? c.warm_tab + li : nullptr;
+    a.grid = a.heads + (a.ww ? 8 * std::max(8, WeightWarm::GROUPS - a.groups) : 0);
+    return a;
+}
+// layer li's q|k|v role; x / x_out null: the layer's input row arrives as pairs (chain launch)
+static QkvFront qkv_front(const DecodeCtx &c, const DecodeLayer &L, int li, float *x, int flags) {
+    return QkvFront{x, x, c.emb_qs, c.emb_d, L.in_norm, L.Wqkv, L.bqkv, c.qkv_pairs + (size_t)li * L.qkv_N, c.eps, c.vocab, L.qkv_N, c.H, qkv_role_grid(L.qkv_N), kv_warm(c, flags, li)};
+}
+// layer li's o-projection role behind grid_attn attention workgroups; residual null: read from the pairs of the previous layer's output row (chain launch)
+static OProjRole oproj_role(const DecodeCtx &c, const DecodeLayer &L, int li, const float *residual, int grid_attn, int rows) {
+    const int K = c.heads * c.D;
+    return OProjRole{L.Wo, residual, c.x1, c.attn_pairs + (size_t)li * K, c.poll_err, c.H, K, grid_attn, rows};
+}
+static DownRole down_role(const DecodeCtx &c, const DecodeLayer &L, int li, int cont) {
+    const int rpw = pjb_rows_per_wg(c.H, c.I);
+    return DownRole{c.act, L.Wdown_raw, c.x1, c.x0, c.x_pairs + (size_t)li * c.H, c.H, c.I, rpw, (c.H + rpw - 1) / rpw, cont};
 }
 
 // argmax of the logits row with the engine's partials scratch: nparts workgroups, then the fold (prefill: into *out; decode: dec_next_kernel folds and advances the state)
@@ -2092,87 +2067,142 @@ int argmax_row_launch(const DecodeCtx &c, const float *logits, int n, int *out, 
     const int rc = argmax_parts_launch(logits, n, c.part_val, c.part_idx, np, st);
     return rc ? rc : argmax_final_launch(c.part_val, c.part_idx, np, out, st);
 }
-static int argmax_and_advance(const DecodeCtx &c, hipStream_t st) {
-    const int np = argmax_parts_count(c);
-    int rc = argmax_parts_launch(c.logits, c.vocab, c.part_val, c.part_idx, np, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dec_next_kernel, dim3(1), dim3(256), 0, st, c.state, c.part_val, c.part_idx, np, c.tok_dev, c.history, c.rope_sin, c.rope_cos, c.cur_sin, c.cur_cos, c.D / 2,
-                       c.cache_limit);
-    return MH_LAUNCH_OK("dec_next");
+
+// one launch of the plan.  x = layer input / output, t = post-attention residual
+int decode_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *layers, const StepLaunch &e, hipStream_t st) {
+    if (e.kind < STEP_HEAD && ((c.D != 128 && c.D != 64) || c.heads % c.kv_heads)) return MLLM_HIP_ERR_SHAPE;
+    float *x = c.x0, *t = c.x1;
+    const int li = e.layer, flags = p.attn_flags;
+    const DecodeLayer &L = layers[li];
+    int rc = 0;
+    switch (e.kind) {
+    case STEP_QKV:
+        NS_DISPATCH(c.H, rc = launch_norm_gemv<NS>(c, L.in_norm, c.eps, L.Wqkv, L.bqkv, L.qkv_N, li == 0, x, x, c.qkv, e.persist, st, kv_warm(c, flags, li)));
+        return rc;
+    case STEP_FRONT: {
+        const AttnRole A = attn_role(c, flags, li, e.ds);
+        const QkvFront F = qkv_front(c, L, li, x, flags);
+        const OProjRole P = oproj_role(c, L, li, x, A.grid, e.o_rows);
+#define FRONT_CASE(DD, EMB)                                                                                                                                   \
+    {                                                                                                                                                         \
+        rc = allow_lds(dec_qkv_attn_oproj_kernel<DD, 2, EMB>, e.lds);                                                                                         \
+        if (rc) return rc;                                                                                                                                    \
+        hipLaunchKernelGGL((dec_qkv_attn_oproj_kernel<DD, 2, EMB>), dim3(F.grid_q + A.grid + oproj_role_grid(P.N, P.rows)), dim3(DEC_PIPE_NT), e.lds, st, c.state, c.cur_sin,     \
+                           c.cur_cos, A.kl, A.vl, c.heads, c.kv_heads, c.cache_limit, c.vt_ld, flags, A.groups, A.ww, F, P);                                  \
+    }
+        if (c.D == 128) FRONT_CASE(128, false) else FRONT_CASE(64, false)
+#undef FRONT_CASE
+        return MH_LAUNCH_OK("dec_qkv_attn_oproj");
+    }
+    case STEP_ATTN: {
+        const AttnRole A = attn_role(c, flags, li, e.ds);
+        if (e.o_rows) {      // the o-projection rides in the attention's launch (K <= 2048: the register form dec_proj_kernel<1, 2, 8>)
+            const OProjRole P = oproj_role(c, L, li, x, A.grid, e.o_rows);
+#define MERGED_O_CASE(DD)                                                                                                                                      \
+    {                                                                                                                                                         \
+        rc = allow_lds(dec_attn_oproj_kernel<DD, 2>, e.lds);                                                                                                  \
+        if (rc) return rc;                                                                                                                                    \
+        hipLaunchKernelGGL((dec_attn_oproj_kernel<DD, 2>), dim3(A.grid + oproj_role_grid(P.N, P.rows)), dim3(DEC_PIPE_NT), e.lds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, A.kl, \
+                           A.vl, c.heads, c.kv_heads, c.cache_limit, c.vt_ld, flags, A.groups, A.ww, P);                                                      \
+    }
+            if (c.D == 128) MERGED_O_CASE(128) else MERGED_O_CASE(64)
+#undef MERGED_O_CASE
+            return MH_LAUNCH_OK("dec_attn_oproj");
+        }
+        const int ds = e.ds;
+        if (e.pipe) {
+#define DEC_PIPE_CASE(DD, DSV)                                                                                                                            \
+    {                                                                                                                                                     \
+        rc = allow_lds(dec_attn_pipe_kernel<DD, DSV>, e.lds);                                                                                             \
+        if (rc) return rc;                                                                                                                                \
+        hipLaunchKernelGGL((dec_attn_pipe_kernel<DD, DSV>), dim3(A.grid), dim3(DEC_PIPE_NT), e.lds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, A.kl, A.vl, c.fa_ws, c.heads,       \
+                           c.kv_heads, c.cache_limit, c.vt_ld, flags, A.groups, A.ww);                                                                    \
+    }
+            if (c.D == 128) { if (ds == 1) DEC_PIPE_CASE(128, 1) else if (ds == 2) DEC_PIPE_CASE(128, 2) else DEC_PIPE_CASE(128, 4) }
+            else { if (ds == 1) DEC_PIPE_CASE(64, 1) else if (ds == 2) DEC_PIPE_CASE(64, 2) else DEC_PIPE_CASE(64, 4) }
+#undef DEC_PIPE_CASE
+            return MH_LAUNCH_OK("dec_attn_pipe");
+        }
+        const int nslots = decode_lds_slots(c.cache_limit, c.D, DEC_ATTN_NT, 2, true);
+        const size_t lds = decode_lds_bytes(c.cache_limit, c.D, DEC_ATTN_NT, 2, nslots, true);
+#define DEC_ATTN_CASE(DD, DSV)                                                                                                                          \
+    {                                                                                                                                                   \
+        rc = allow_lds(dec_attn_kernel<DD, DSV>, lds);                                                                                                  \
+        if (rc) return rc;                                                                                                                              \
+        hipLaunchKernelGGL((dec_attn_kernel<DD, DSV>), dim3(A.heads), dim3(DEC_ATTN_NT), lds, st, c.state, c.qkv, c.cur_sin, c.cur_cos, A.kl, A.vl, c.fa_ws, c.heads, \
+                           c.kv_heads, c.cache_limit, c.vt_ld, nslots, flags);                                                                          \
+    }
+        if (c.D == 128) { if (ds == 1) DEC_ATTN_CASE(128, 1) else if (ds == 2) DEC_ATTN_CASE(128, 2) else DEC_ATTN_CASE(128, 4) }
+        else { if (ds == 1) DEC_ATTN_CASE(64, 1) else if (ds == 2) DEC_ATTN_CASE(64, 2) else DEC_ATTN_CASE(64, 4) }
+#undef DEC_ATTN_CASE
+        return MH_LAUNCH_OK("dec_attn");
+    }
+    case STEP_OPROJ:
+        NS_DISPATCH(c.heads * c.D, rc = (launch_proj<NS>(L.Wo, L.Wo_raw, c.fa_ws, x, t, c.H, c.heads * c.D, e.blk, st)));
+        return rc;
+    case STEP_GATEUP:
+        NS_DISPATCH(c.H, rc = launch_gateup<NS>(L, c, t, e.blk, e.persist, st));
+        return rc;
+    case STEP_DOWN:
+        NS_DISPATCH(c.I, rc = (launch_proj<NS>(L.Wdown, L.Wdown_raw, c.act, t, x, c.H, c.I, e.blk, st)));
+        return rc;
+    case STEP_CHAIN: {      // layer li's down projection + layer li + 1's q|k|v + attention + o-projection
+        const int ln = li + 1;
+        const AttnRole A = attn_role(c, flags, ln, e.ds);
+        const DownRole Dn = down_role(c, L, li, e.cont);
+        const QkvFront F = qkv_front(c, layers[ln], ln, nullptr, flags);
+        const OProjRole P = oproj_role(c, layers[ln], ln, nullptr, A.grid, e.o_rows);
+#define CHAIN_CASE(DD, NSV)                                                                                                                                   \
+    {                                                                                                                                                         \
+        rc = allow_lds(dec_down_front_kernel<DD, 2, NSV>, e.lds);                                                                                             \
+        if (rc) return rc;                                                                                                                                    \
+        hipLaunchKernelGGL((dec_down_front_kernel<DD, 2, NSV>), dim3(Dn.grid_d + (Dn.cont ? 0 : F.grid_q) + A.grid + oproj_role_grid(P.N, P.rows)), dim3(DEC_PIPE_NT), e.lds, st, \
+                           c.state, c.cur_sin, c.cur_cos, A.kl, A.vl, c.heads, c.kv_heads, c.cache_limit, c.vt_ld, flags, A.groups, A.ww, Dn, F, P);          \
+    }
+        const int NSd = (c.I / 256 + 7) / 8;
+        if (c.D == 128) { if (NSd == 3) CHAIN_CASE(128, 3) else if (NSd == 4) CHAIN_CASE(128, 4) else CHAIN_CASE(128, 5) }
+        else { if (NSd == 3) CHAIN_CASE(64, 3) else if (NSd == 4) CHAIN_CASE(64, 4) else CHAIN_CASE(64, 5) }
+#undef CHAIN_CASE
+        return MH_LAUNCH_OK("dec_down_front");
+    }
+    case STEP_HEAD:
+        if (e.head == 0) {      // model.norm -> Q8_K -> Q4_K rows, the same fused kernel as the q|k|v projection
+            NS_DISPATCH(c.H, rc = launch_norm_gemv<NS>(c, c.final_norm, c.final_eps, c.Whead, nullptr, c.vocab, false, x, x, c.logits, e.persist, st));
+            return rc;
+        }
+        if (e.head == 1) {      // the stand-alone launchers (same arithmetic)
+            rc = mllm_hip_rmsnorm(x, c.final_norm, c.normed, nullptr, nullptr, nullptr, 1, c.H, c.final_eps, 0, st);
+            if (!rc) rc = mllm_hip_quantize_q80(c.normed, c.x80_qs, c.x80_d, 1, c.H, st);
+            if (!rc) rc = mllm_hip_linear_q40_q80(c.emb_qs, c.emb_d, nullptr, c.x80_qs, c.x80_d, c.logits, c.vocab, 1, c.vocab, c.H, st);
+            return rc;
+        }
+        {
+            if (e.parts > c.max_parts) return MLLM_HIP_ERR_SHAPE;
+            const size_t lds = (((size_t)c.H * 5 + (size_t)c.H / 32 * 4 + 15) & ~(size_t)15) + 4 * q40_tab_floats(c.H / 32) * sizeof(float);
+#define HEAD_CASE(B) case B: rc = allow_lds(dec_head_kernel<B>, lds); if (rc) return rc; hipLaunchKernelGGL((dec_head_kernel<B>), dim3(e.parts), dim3(256), lds, st, x, c.final_norm, c.final_eps, c.emb_qs, c.emb_d, c.logits, c.part_val, c.part_idx, c.vocab, c.H, e.rows); break;
+            switch (c.H / 512) { HEAD_CASE(1) HEAD_CASE(2) HEAD_CASE(3) HEAD_CASE(4) HEAD_CASE(5) HEAD_CASE(6) HEAD_CASE(7) HEAD_CASE(8) }
+#undef HEAD_CASE
+            return MH_LAUNCH_OK("dec_head");
+        }
+    case STEP_NEXT: {      // fold the partial maxima (the fused head's, else those of an argmax launch over the logits row) and advance the state
+        const int np = e.parts ? e.parts : argmax_parts_count(c);
+        if (!e.parts && (rc = argmax_parts_launch(c.logits, c.vocab, c.part_val, c.part_idx, np, st))) return rc;
+        hipLaunchKernelGGL(dec_next_kernel, dim3(1), dim3(256), 0, st, c.state, c.part_val, c.part_idx, np, c.tok_dev, c.history, c.rope_sin, c.rope_cos, c.cur_sin, c.cur_cos, c.D / 2,
+                           c.cache_limit);
+        return MH_LAUNCH_OK("dec_next");
+    }
+    }
+    return MLLM_HIP_ERR_ARG;
 }
 
-// which slot (layer, kernel) of the step is a launch of its own, and of which kind (StepMarks): the merged forms leave the slots they swallow empty
-static int step_slot_kind(const DecodeCtx &c, const DecodeLayer *layers, int li, int k) {
-    const bool chained = decode_merges_chain(c, layers, li - 1), front = !chained && decode_merges_front(c, layers[li], li);
-    switch (k) {
-    case 0: return chained ? -1 : (front ? 6 : 0);
-    case 1: return chained || front ? -1 : 1;
-    case 2: return chained || front || decode_merges_o(c) ? -1 : 2;
-    case 3: return 3;
-    default: return decode_merges_chain(c, layers, li) ? 5 : 4;
+int decode_step_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *layers, hipStream_t st, const StepMarks *marks) {
+    for (const StepLaunch &e : p.launches) {
+        int rc = marks ? marks->mark(marks->user, e.kind, 0) : 0;
+        if (!rc) rc = decode_launch(c, p, layers, e, st);
+        if (!rc && marks) rc = marks->mark(marks->user, e.kind, 1);
+        if (rc) return rc;
     }
-}
-int decode_step_launch(const DecodeCtx &c, const DecodeLayer *layers, int n_layers, hipStream_t st, const StepMarks *marks) {
-    float *x = c.x0;
-    int rc = 0;
-#define MARK(kind, after) do { if (marks && (rc = marks->mark(marks->user, kind, after))) return rc; } while (0)
-    for (int li = 0; li < n_layers; ++li)
-        for (int k = 0; k < 5; ++k) {
-            const int kind = marks ? step_slot_kind(c, layers, li, k) : -1;
-            if (kind >= 0) MARK(kind, 0);
-            rc = decode_kernel_launch(c, layers, li, k, st);
-            if (rc) return rc;
-            if (kind >= 0) MARK(kind, 1);
-        }
-    if (c.Whead) {
-        // Linear lm_head (LLaMA-style models): model.norm -> Q8_K -> Q4_K rows, the same fused kernel as the q|k|v projection; then argmax
-        MARK(7, 0);
-        NS_DISPATCH(c.H, rc = launch_norm_gemv<NS>(c, c.final_norm, c.final_eps, c.Whead, nullptr, c.vocab, false, x, x, c.logits, st));
-        if (rc) return rc;
-        MARK(7, 1);
-        MARK(8, 0);
-        rc = argmax_and_advance(c, st);
-        if (rc) return rc;
-        MARK(8, 1);
-        return 0;
-    }
-    // tied lm_head + argmax
-    if (c.H % 512 != 0 || c.H / 512 > 8) {
-        // shapes the fused head kernel does not cover: the stand-alone launchers (same arithmetic), then advance the state
-        MARK(7, 0);
-        rc = mllm_hip_rmsnorm(x, c.final_norm, c.normed, nullptr, nullptr, nullptr, 1, c.H, c.final_eps, 0, st);
-        if (!rc) rc = mllm_hip_quantize_q80(c.normed, c.x80_qs, c.x80_d, 1, c.H, st);
-        if (!rc) rc = mllm_hip_linear_q40_q80(c.emb_qs, c.emb_d, nullptr, c.x80_qs, c.x80_d, c.logits, c.vocab, 1, c.vocab, c.H, st);
-        if (rc) return rc;
-        MARK(7, 1);
-        MARK(8, 0);
-        rc = argmax_and_advance(c, st);
-        if (rc) return rc;
-        MARK(8, 1);
-        return 0;
-    }
-    const int head_wpc = option(OPT_HEAD_WPC) > 0 ? option(OPT_HEAD_WPC) : 8;   // waves per CU the row split aims at
-    const int target_waves = 256 * head_wpc;
-    int rpw = (c.vocab + target_waves - 1) / target_waves;
-    rpw = ((rpw + 7) / 8) * 8;
-    const int waves = (c.vocab + rpw - 1) / rpw, blocks = (waves + 3) / 4;
-    if (blocks > c.max_parts) return MLLM_HIP_ERR_SHAPE;
-    const size_t lds = (((size_t)c.H * 5 + (size_t)c.H / 32 * 4 + 15) & ~(size_t)15) + 4 * q40_tab_floats(c.H / 32) * sizeof(float);
-#define HEAD_CASE(B) case B: rc = allow_lds(dec_head_kernel<B>, lds); if (rc) return rc; hipLaunchKernelGGL((dec_head_kernel<B>), dim3(blocks), dim3(256), lds, st, x, c.final_norm, c.final_eps, c.emb_qs, c.emb_d, c.logits, c.part_val, c.part_idx, c.vocab, c.H, rpw); break;
-    MARK(7, 0);
-    switch (c.H / 512) { HEAD_CASE(1) HEAD_CASE(2) HEAD_CASE(3) HEAD_CASE(4) HEAD_CASE(5) HEAD_CASE(6) HEAD_CASE(7) HEAD_CASE(8) }
-#undef HEAD_CASE
-    rc = MH_LAUNCH_OK("dec_head");
-    if (rc) return rc;
-    MARK(7, 1);
-    MARK(8, 0);
-    hipLaunchKernelGGL(dec_next_kernel, dim3(1), dim3(256), 0, st, c.state, c.part_val, c.part_idx, blocks, c.tok_dev, c.history, c.rope_sin, c.rope_cos, c.cur_sin, c.cur_cos,
-                       c.D / 2, c.cache_limit);
-    rc = MH_LAUNCH_OK("dec_next");
-    if (rc) return rc;
-    MARK(8, 1);
     return 0;
-#undef MARK
 }
 }  // namespace mllm_hip
 

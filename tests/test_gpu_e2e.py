@@ -308,6 +308,30 @@ def test_lane_per_superblock_projection_on_short_rows(tmp_path):
         lib.set_option("pjb_min_ns", -1)
 
 
+def test_time_kernel_takes_the_five_layer_kernels_and_nothing_else(tmp_path):
+    """mllm_hip_model_time_kernel: which = 10..14 are the five kernels of a layer as launches of their own; the step's other kinds of launch (the shared launches, the head,
+    the state advance) are not offered -- 15.. is an argument error and issues nothing: the decode step that follows is the golden run's."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qwen2vl_tiny.npz"))
+    cfg = synth.qwen2vl_tiny()
+    m = lib.Qwen2VL(cfg, weights.qwen2vl_file(cfg, cache_dir=str(tmp_path)))
+    try:
+        tok, logits, _ = m.prefill(g["ids_text"])
+        assert np.array_equal(logits, g["logits_text"][0])
+        n = len(g["tokens_text"])
+        for s in range(1, n):
+            if s == n - 1:      # refused before anything is issued: the step behind it still matches
+                for which in (15, 16, 17, 18, 19, 99):
+                    with pytest.raises(lib.MllmHipError):
+                        m.time_kernel(which, 2)
+            tok, logits, _ = m.decode(tok)
+            assert np.array_equal(logits, g["logits_text"][s]), s
+        for which in (10, 11, 12, 13, 14):      # (last: these write the activation rows and the cache row of the step they stand for)
+            ms, nbytes = m.time_kernel(which, 2)
+            assert ms > 0 and nbytes > 0, which
+    finally:
+        m.close()
+
+
 # ---- the full-range toy file (synthfile full_range=True; tests/golden/qwen2vl_tiny_fr.npz): the reference's greedy id changes from step to step, so a step that embeds a
 # stale id (the previous step's, the prefill's, the captured graph's input) or a launch form that feeds the wrong token cannot pass ------------------------------------
 GOLD_FR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qwen2vl_tiny_fr.npz")
