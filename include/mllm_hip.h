@@ -234,6 +234,9 @@ int mllm_hip_rope_table_ntk(float theta, int dim, int n_pos, int original_max_po
                             float *sin_host, float *cos_host);
 int mllm_hip_mrope_table(float base, int dim, const float *pos3xS_host, int S, const int *section, int n_section,
                          float *sin_host, float *cos_host);
+/* the M-RoPE rows of the decode steps, `[n_pos][dim/2]`: row p is mllm_hip_mrope_table's row for position p on all three axes (what get_position_ids' decode
+ * branch produces, modeling_qwen2_vl.hpp:423-432).  The batched step keeps it resident and indexes it by each sequence's position on the device. */
+int mllm_hip_mrope_decode_table(float base, int dim, int n_pos, const int *section, int n_section, float *sin_host, float *cos_host);
 int mllm_hip_vision_rope_table(int t, int h, int w, int merge, int rot_dim, float *sin_host, float *cos_host);
 /* the VISIONROPE layer's own output (CPUVisionRoPE.cpp:19-147): the angle table `[t*h*w][rot_dim]` (h angles, then w angles) whose sin / cos
  * F_APPLY_VISIOROPE evaluates per use (CPUVisionRoPEFunc.hpp:21-60); mllm_hip_vision_rope_table = sinf / cosf of these */
@@ -362,10 +365,24 @@ int mllm_hip_model_decode(mllm_hip_model *m, int32_t token, float *logits_host, 
  * mllm_hip_model_prefill / _decode / _generate / _clear_kvcache / _cache_len act on (so every sequence is prefilled with the ordinary call, image prompts included);
  * batch_decode(B, tokens) steps sequences 0 .. B-1 together: tokens[b] is appended to sequence b, logits_host (optional) receives `[B][vocab]`, next_tokens (optional)
  * the B greedy ids.  Rows never mix (attention runs per sequence on its own cache; every other Op is row-wise), so row b equals, bit for bit, what sequence b
- * produces stepping alone.  The single-sequence fused decode step stays the headline path; this is the aggregate-throughput form. */
+ * produces stepping alone.  The single-sequence fused decode step stays the headline path; this is the aggregate-throughput form.
+ * What a step needs lives in device memory -- per sequence {slabs, tokens in the cache, rotary position, active, steps made}, the id to embed, one rotary table
+ * `[cache_limit][D/2]` per model indexed by the sequence's position -- and the step's last launch advances it, so batch_decode and batch_generate issue the same
+ * launches; batch_decode uploads its tokens and the host's counters first and may stay eager. */
 int mllm_hip_model_batch_begin(mllm_hip_model *m, int B);
 int mllm_hip_model_batch_select(mllm_hip_model *m, int seq);
 int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens, float *logits_host, int32_t *next_tokens, float *elapsed_ms);
+/* Greedy generation for sequences 0 .. B-1 together, resident on the device: the loop of Module::generate (mllm/Module.cpp:63-100) over KVCache_batch sequences
+ * (mllm/Types.hpp:26-33).  Each sequence has been prefilled as for batch_decode.  Step 0 appends first_tokens[b] to sequence b, every later step the greedy id (first
+ * maximum, std::max_element) the step before produced for that row; tokens_host is `[B][steps]`, tokens_host[b][s] = the id sequence b's step s produced.  One
+ * captured graph per B replays every step (MLLM_HIP_NO_GRAPH: eager); nothing crosses PCIe between steps.
+ * eos < 0: every sequence runs `steps` steps.  eos >= 0: a sequence that produces eos at step s keeps that id in tokens_host[b][s], gets n_out[b] = s + 1 and takes no
+ * further step (its cache and position stop there; the rest of its row is -1); the call returns early once every sequence has stopped, which it learns from one
+ * 4-byte read every 16 steps.  Afterwards cache_len of sequence b has grown by n_out[b], and every sequence can carry on by batch_decode, another batch_generate
+ * (any B) or batch_select + decode / generate with the bits it would have had stepping alone.  n_out, tokens_host and elapsed_ms (device time between events either
+ * side of the steps) may be NULL.  ERR_ARG: NULL model / first_tokens, no LLM, B < 1 or above batch_begin's, steps <= 0, a sequence without a prefill; ERR_SHAPE:
+ * cache_len[b] + steps > cache_limit for some b (nothing changed).  After a failure inside the loop the host's counters are re-read from the device state. */
+int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out, float *elapsed_ms);
 /* `steps` greedy decode forwards back to back on the device (argmax on device, no per-token D2H): SURVEY N2, the loop of
  * Module::generate (mllm/Module.cpp:63-100) with the greedy method.  tokens_host receives the generated ids. */
 int mllm_hip_model_generate(mllm_hip_model *m, int32_t first_token, int steps, int32_t *tokens_host, float *elapsed_ms);

@@ -99,15 +99,30 @@ int argmax_row_launch(const DecodeCtx &c, const float *logits, int n, int *out, 
 struct StepMarks { int (*mark)(void *user, int kind, int after); void *user; };
 int decode_step_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *layers, hipStream_t st, const StepMarks *marks = nullptr);
 
-// ---- batched decode (engine.hip: mllm_hip_model_batch_decode): the one Op of a step that is not row-wise, for all B sequences in one launch each ----
-// one sequence's KV slabs (bases of layer 0) and the tokens its cache holds BEFORE this step
-struct SeqKV { uint16_t *k; uint16_t *v; int t; int pad; };
+// ---- batched decode (engine.hip: mllm_hip_model_batch_decode / _batch_generate): the launches of a B-row step that are not row-wise Ops ----
+// One sequence's state in device memory.  The kernels read it from there (never from kernel arguments), so a captured step neither bakes a sequence's slabs in nor
+// needs the host between steps: seqs_next_kernel advances it.  The id to embed at the next step is not kept here: it lives as the fp32 id mllm_hip_embedding_q40 reads.
+struct SeqKV {
+    uint16_t *k; uint16_t *v;   // the sequence's KV slabs (bases of layer 0)
+    int t;                      // tokens its cache holds BEFORE this step
+    int pos;                    // rotary position of the token this step appends (row of the resident table; after an image prompt smaller than t)
+    int active;                 // 0: stopped at the end-of-sequence id -- the step leaves its cache and counters alone
+    int made;                   // steps made since the state was uploaded (the column of its history row)
+};
+// what the whole batch shares: the end-of-sequence id (< 0: none) and the rows still active after the last step (the host reads it every few steps)
+struct BatchCtl { int eos; int n_active; };
 // row b of qkv ([B][ldq]: q | k | v of sequence b's new token): q rotated in place, k rotated -> fp16 row t_b of sequence b's K slab, v -> column t_b of its transposed V slab
-// (qkv_rope_append_kernel's arithmetic, S = 1 per sequence; rotary row b of sin_t / cos_t)
-int seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, const SeqKV *seqs_dev, int64_t layer_k_off, int64_t layer_v_off,
-                            int64_t ldk, int64_t ldvt, int B, int Hq, int Hkv, int D, hipStream_t st);
+// (qkv_rope_append_kernel's arithmetic, S = 1 per sequence).  sin_t / cos_t: the resident table [tab_rows][ld_tab], row = the sequence's pos.  A stopped sequence, or one
+// whose cache is full (t >= cap), is skipped.
+int seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, int tab_rows, const SeqKV *seqs_dev, int64_t layer_k_off,
+                            int64_t layer_v_off, int64_t ldk, int64_t ldvt, int B, int Hq, int Hkv, int D, int cap, hipStream_t st);
 // __fa2_decode of row b's query over sequence b's t_b + 1 keys (fa2_decode_kernel's body, grid = heads x sequences); cap = the slabs' capacity in keys
 int seqs_fa2_decode_launch(const float *q, int64_t ldq, const SeqKV *seqs_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o, int64_t ldo, int B,
                            int Hq, int Hkv, int D, int cap, hipStream_t st);
+// first-maximum argmax of the B logits rows and the state advance, two launches: partial maxima over (nparts, B) workgroups, then one workgroup (a wave per row) folds row
+// b's partials, writes the id to tok_out[b], history[b][made_b] and ids_f[b] (the next step's embedding input), advances t / pos / made of the active rows and clears
+// `active` on the end-of-sequence id.  part_val / part_idx hold B * nparts entries; B <= 16.
+int seqs_argmax_next_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, SeqKV *seqs_dev, BatchCtl *ctl, int *tok_out,
+                            float *ids_f, int *history, int hist_ld, hipStream_t st);
 
 }  // namespace mllm_hip

@@ -236,6 +236,10 @@ struct mllm_hip_model {
     SeqKV *seqkv_dev = nullptr;
     bool needs_arm = false;      // a batched step moved the selected sequence on: the fused decode step's device state is re-armed before its next use
     float *blogits = nullptr, *bnormed = nullptr; int8_t *bx80_qs = nullptr; uint16_t *bx80_d = nullptr; int *btok = nullptr; int batch_cap = 0;
+    // the batched step's device state beside the SeqKV descriptors: the rotary table [cache_limit][D/2] (built on first batched use), the batch's control words, the ids
+    // of a batch_generate [batch_cap][cache_limit]; its captured step (one live graph, for bgraph_B rows; a B is captured once a step of that B has run eagerly)
+    float *btab_sin = nullptr, *btab_cos = nullptr; BatchCtl *bctl = nullptr; int *bhist = nullptr;
+    hipGraph_t bgraph = nullptr; hipGraphExec_t bgraph_exec = nullptr; int bgraph_B = 0; unsigned beager = 0;
     int64_t decode_weight_bytes = 0, resident_bytes = 0, released_bytes = 0;      // device bytes held after the load / raw rows and packs not kept (load_linear_q4k)
     float load_total_ms = 0, load_h2d_ms = 0, load_tail_ms = 0;
 
@@ -588,6 +592,8 @@ extern "C" void mllm_hip_model_destroy(mllm_hip_model *m) {
     if (m->st) (void)hipStreamSynchronize(m->st);
     if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
     if (m->graph) (void)hipGraphDestroy(m->graph);
+    if (m->bgraph_exec) (void)hipGraphExecDestroy(m->bgraph_exec);
+    if (m->bgraph) (void)hipGraphDestroy(m->bgraph);
     for (void *p : m->allocs) (void)hipFree(p);
     for (void *p : m->vis_allocs) (void)hipFree(p);
     for (void *p : m->temps) (void)hipFree(p);
@@ -660,10 +666,12 @@ static void rope_index(const M *m, const int32_t *ids, int S, const int32_t *gri
 // ---- quantised activations feeding a Linear.  Rows >= 16 meet the GEMM, whose activation operand is a packed layout: the
 // producers (norms with fused quantisation, the quantiser) then write that layout directly into m->xpack (one scratch: every
 // quantised buffer is consumed by the very next Linear); fewer rows take the GEMV on the three Q8_K planes.
+static int drop_batch_graph(M *m);
 static int ensure_xpack(M *m, int rows, int K) {
     const size_t need_b = mllm_hip_q4k_prepack_bytes(rows, K);
-    if (need_b > m->xpack_bytes) {   // grown on demand (prefill only, never inside a captured graph)
+    if (need_b > m->xpack_bytes) {   // grown on demand (prefill, or the eager first batched step of a B; never inside a captured graph)
         HH(hipStreamSynchronize(m->st));
+        EH(drop_batch_graph(m));      // a captured batched step of four rows and more holds the scratch's address
         if (m->xpack) HH(hipFree(m->xpack));
         m->xpack = nullptr; m->xpack_bytes = 0;
         HH(hipMalloc(&m->xpack, need_b));
@@ -1164,6 +1172,8 @@ extern "C" int mllm_hip_model_time_step(mllm_hip_model *m, int32_t first_token, 
 // runs per sequence on that sequence's own cache -- so row b of a batched step is bit for bit what sequence b would have produced stepping alone (tests/test_batched_decode.py).
 // The step is composed from the per-Op launchers like the prefill (the M < 16 GEMV form reads each weight row once for all B rows); the fused single-sequence decode
 // kernels and their captured graph stay the headline path (bench.py's `value`); `batched_decode` is reported beside it.
+// What a step needs lives in device memory (decode_launch.h: SeqKV per sequence, BatchCtl, the fp32 ids, one rotary table per model) and the step's last launch advances
+// it, so batch_decode (uploads the host's tokens and counters, eager) and batch_generate (uploads once, one captured graph per B replays every step) share batch_step_body.
 static void seq_park(M *m) {
     if (m->seqs.empty()) m->seqs.resize(1);
     auto &q = m->seqs[m->cur_seq];
@@ -1184,6 +1194,15 @@ static int seq_select(M *m, int s) {
     }
     return 0;
 }
+static int drop_batch_graph(M *m) {
+    if (m->bgraph_exec) {
+        HH(hipStreamSynchronize(m->st));
+        HH(hipGraphExecDestroy(m->bgraph_exec)); m->bgraph_exec = nullptr;
+    }
+    if (m->bgraph) { HH(hipGraphDestroy(m->bgraph)); m->bgraph = nullptr; }
+    m->bgraph_B = 0;
+    return 0;
+}
 extern "C" int mllm_hip_model_batch_begin(mllm_hip_model *m, int B) {
     if (!m || !m->has_llm || B < 1 || B > 15) return MLLM_HIP_ERR_ARG;      // 15: the rows of a step go through the M < 16 GEMV form
     const auto &c = m->c;
@@ -1197,10 +1216,26 @@ extern "C" int mllm_hip_model_batch_begin(mllm_hip_model *m, int B) {
         m->seqs.push_back(q);
     }
     if (B > m->batch_cap) {
+        EH(drop_batch_graph(m));      // it holds the addresses of the buffers that are replaced here
         EH(m->dalloc(&m->blogits, (size_t)B * c.vocab * 4)); EH(m->dalloc(&m->bnormed, (size_t)B * c.hidden * 4));
         EH(m->dalloc(&m->bx80_qs, (size_t)B * c.hidden)); EH(m->dalloc(&m->bx80_d, (size_t)B * (c.hidden / 32) * 2 + 64)); EH(m->dalloc(&m->btok, (size_t)B * 4));
         EH(m->dalloc(&m->seqkv_dev, (size_t)B * sizeof(SeqKV)));
+        EH(m->dalloc(&m->bhist, (size_t)B * c.cache_limit * 4));
         m->batch_cap = B;
+    }
+    if (!m->btab_sin) {
+        // the rotary row of every position a decode step can take, resident: HF rotary = CPURoPE's static table; QWEN2VL = the M-RoPE row of position p on all three axes
+        const int half = m->D / 2;
+        const size_t n = (size_t)c.cache_limit * half;
+        EH(m->dalloc(&m->bctl, sizeof(BatchCtl)));
+        EH(m->dalloc(&m->btab_sin, n * 4)); EH(m->dalloc(&m->btab_cos, n * 4));
+        if (m->mrope) {
+            std::vector<float> s(n), co(n);
+            EH(mllm_hip_mrope_decode_table(c.rope_theta, m->D, c.cache_limit, c.mrope_section, 3, s.data(), co.data()));
+            HH(hipMemcpy(m->btab_sin, s.data(), n * 4, hipMemcpyHostToDevice)); HH(hipMemcpy(m->btab_cos, co.data(), n * 4, hipMemcpyHostToDevice));
+        } else {
+            HH(hipMemcpy(m->btab_sin, m->hf_sin.data(), n * 4, hipMemcpyHostToDevice)); HH(hipMemcpy(m->btab_cos, m->hf_cos.data(), n * 4, hipMemcpyHostToDevice));
+        }
     }
     HH(hipStreamSynchronize(m->st));
     return MLLM_HIP_OK;
@@ -1211,41 +1246,47 @@ extern "C" int mllm_hip_model_batch_select(mllm_hip_model *m, int seq) {
     if (seq < 0 || seq >= (int)m->seqs.size()) return MLLM_HIP_ERR_ARG;
     return seq_select(m, seq);
 }
-extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
-    if (!m || !m->has_llm || !tokens || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
-    const auto &c = m->c;
+// what both batched entry points refuse before the first HIP call
+static int batch_check(M *m, int B, int steps, const char *who) {
     seq_park(m);
     if ((int)m->seqs.size() < B) return MLLM_HIP_ERR_ARG;
+    for (int b = 0; b < B; ++b)
+        if (m->seqs[b].cache_len <= 0) { set_error_msg("%s: sequence %d has no prefill", who, b); return MLLM_HIP_ERR_ARG; }
+    for (int b = 0; b < B; ++b)
+        if (m->seqs[b].cache_len + steps > m->c.cache_limit) {
+            fprintf(stderr, "mllm_hip: KV cache overflow (%d + %d > %d)\n", m->seqs[b].cache_len, steps, m->c.cache_limit);
+            return MLLM_HIP_ERR_SHAPE;
+        }
+    return 0;
+}
+// the rotary position of the token sequence q appends next (QWEN2VL: all three axes = last_pos + 1, modeling_qwen2_vl.hpp:423-432; HF rotary: the tokens in its cache)
+static int seq_next_pos(const M *m, const M::Seq &q) { return m->mrope ? (int)q.last_pos + 1 : q.cache_len; }
+// the host's counters and the tokens to embed -> the device state of sequences 0 .. B-1 (every one active, no step made); synchronised: the host vectors go out of
+// scope, and the inputs are resident when the clock starts
+static int batch_upload_state(M *m, int B, const int32_t *tokens, int32_t eos) {
+    std::vector<float> idf(B);
+    std::vector<SeqKV> desc(B);
     for (int b = 0; b < B; ++b) {
-        if (m->seqs[b].cache_len <= 0) { set_error_msg("mllm_hip_model_batch_decode: sequence %d has no prefill", b); return MLLM_HIP_ERR_ARG; }
-        if (m->seqs[b].cache_len + 1 > c.cache_limit) { fprintf(stderr, "mllm_hip: KV cache overflow (%d + 1 > %d)\n", m->seqs[b].cache_len, c.cache_limit); return MLLM_HIP_ERR_SHAPE; }
+        idf[b] = (float)tokens[b];
+        desc[b] = SeqKV{m->seqs[b].kslab, m->seqs[b].vslab, m->seqs[b].cache_len, seq_next_pos(m, m->seqs[b]), 1, 0};
     }
+    const BatchCtl ctl = {eos, B};
+    HH(hipMemcpyAsync(m->ids_f, idf.data(), (size_t)B * 4, hipMemcpyHostToDevice, m->st));
+    HH(hipMemcpyAsync(m->seqkv_dev, desc.data(), (size_t)B * sizeof(SeqKV), hipMemcpyHostToDevice, m->st));
+    HH(hipMemcpyAsync(m->bctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, m->st));
+    HH(hipStreamSynchronize(m->st));
+    return 0;
+}
+// The launches of one batched step, all on the engine's stream and each a plain dependent launch: the row-wise Ops of the prefill's per-Op launchers over B rows, per
+// layer the rotary + cache append and the attention of all B sequences (one launch each, the sequences' slabs / positions read from their device state), the head, then
+// the B argmaxes in one launch and the fold that advances the device state.  batch_decode issues it eagerly, batch_generate replays it as a captured graph.
+static int batch_step_body(M *m, int B) {
+    const auto &c = m->c;
     const int H = c.hidden, I = c.inter, D = m->D, half = D / 2;
     hipStream_t st = m->st;
-    // the rotary row of every sequence's next position (QWEN2VL: all three axes = last_pos + 1, modeling_qwen2_vl.hpp:423-432; HF rotary: position = tokens in its cache)
-    std::vector<float> idf(B), s((size_t)B * half), co((size_t)B * half);
-    for (int b = 0; b < B; ++b) idf[b] = (float)tokens[b];
-    if (m->mrope) {
-        std::vector<float> pos((size_t)3 * B);
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < B; ++b) pos[(size_t)a * B + b] = m->seqs[b].last_pos + 1.0f;
-        EH(mllm_hip_mrope_table(c.rope_theta, D, pos.data(), B, c.mrope_section, 3, s.data(), co.data()));
-    } else {
-        for (int b = 0; b < B; ++b) {
-            memcpy(s.data() + (size_t)b * half, m->hf_sin.data() + (size_t)m->seqs[b].cache_len * half, (size_t)half * 4);
-            memcpy(co.data() + (size_t)b * half, m->hf_cos.data() + (size_t)m->seqs[b].cache_len * half, (size_t)half * 4);
-        }
-    }
-    HH(hipMemcpyAsync(m->rope_sin, s.data(), s.size() * 4, hipMemcpyHostToDevice, st));
-    HH(hipMemcpyAsync(m->rope_cos, co.data(), co.size() * 4, hipMemcpyHostToDevice, st));
-    HH(hipMemcpyAsync(m->ids_f, idf.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    std::vector<SeqKV> desc(B);
-    for (int b = 0; b < B; ++b) desc[b] = SeqKV{m->seqs[b].kslab, m->seqs[b].vslab, m->seqs[b].cache_len, 0};
-    HH(hipMemcpyAsync(m->seqkv_dev, desc.data(), (size_t)B * sizeof(SeqKV), hipMemcpyHostToDevice, st));
-    HH(hipStreamSynchronize(st));      // the host vectors go out of scope; inputs resident when the clock starts
     // from four rows on the Linears take the packed MFMA GEMM: its 32-row tile costs the same for 1 .. 32 rows, the M < 16 GEMV form pays its chain tables per row
     struct MinRows { M *m; int keep; ~MinRows() { m->gemm_min_rows = keep; } } restore{m, m->gemm_min_rows};
     if (B >= 4) m->gemm_min_rows = B;
-    HH(hipEventRecord(m->ev0, st));
     EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, B, H, c.vocab, st));
     float *h = m->h0, *h2 = m->h1;
     for (int li = 0; li < c.layers; ++li) {
@@ -1254,7 +1295,8 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
         EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, B));
         // attention is the one Op that is not row-wise: sequence b's new key / value go to ITS slabs at ITS position, its query walks ITS cache -- all B in one launch each
         const int64_t koff = (int64_t)li * c.cache_limit * m->KVD, voff = (int64_t)li * m->KVD * m->vt_ld;
-        EH(seqs_rope_append_launch(m->qkv, m->QKV, m->rope_sin, m->rope_cos, half, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, B, c.heads, c.kv_heads, D, st));
+        EH(seqs_rope_append_launch(m->qkv, m->QKV, m->btab_sin, m->btab_cos, half, c.cache_limit, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, B, c.heads, c.kv_heads, D,
+                                   c.cache_limit, st));
         EH(seqs_fa2_decode_launch(m->qkv, m->QKV, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, B, c.heads, c.kv_heads, D, c.cache_limit, st));
         EH(q_quant(m, m->attn, m->xq, B, m->HD));
         EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, B));
@@ -1271,7 +1313,18 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
         EH(mllm_hip_rmsnorm(h, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, B, H, c.final_eps, 0, st));
         EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->blogits, MLLM_HIP_F32, c.vocab, nullptr, B, c.vocab, H, st));
     }
-    for (int b = 0; b < B; ++b) EH(argmax_row_launch(m->dctx, m->blogits + (size_t)b * c.vocab, c.vocab, m->btok + b, st));
+    const int np = std::max(1, std::min(m->max_parts / B, 128));
+    return seqs_argmax_next_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
+}
+extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
+    if (!m || !m->has_llm || !tokens || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
+    EH(batch_check(m, B, 1, "mllm_hip_model_batch_decode"));
+    const auto &c = m->c;
+    hipStream_t st = m->st;
+    EH(batch_upload_state(m, B, tokens, -1));
+    HH(hipEventRecord(m->ev0, st));
+    EH(batch_step_body(m, B));
+    m->beager |= 1u << B;
     HH(hipEventRecord(m->ev1, st));
     if (logits_host) HH(hipMemcpyAsync(logits_host, m->blogits, (size_t)B * c.vocab * 4, hipMemcpyDeviceToHost, st));
     if (next_tokens) HH(hipMemcpyAsync(next_tokens, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
@@ -1279,6 +1332,76 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
     for (int b = 0; b < B; ++b) { m->seqs[b].cache_len += 1; m->seqs[b].last_pos += 1.0f; }
     if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+    return MLLM_HIP_OK;
+}
+
+// One step of batch_generate.  The first step of a given B on this model runs eagerly (the Ops' one-time work -- growing the GEMM's activation scratch, function
+// attributes -- must not sit inside a capture); from the second on the step is one captured graph, a single chain on the engine's stream, re-captured when B changes.
+static int batch_step(M *m, int B) {
+    const unsigned bit = 1u << B;
+    if (!m->use_graph || !(m->beager & bit)) {
+        EH(batch_step_body(m, B));
+        m->beager |= bit;
+        return 0;
+    }
+    if (m->bgraph_B != B) {
+        EH(drop_batch_graph(m));
+        HH(hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal));
+        const int rc = batch_step_body(m, B);
+        const hipError_t e = hipStreamEndCapture(m->st, &m->bgraph);
+        if (rc) { (void)drop_batch_graph(m); return rc; }
+        HH(e);
+        HH(hipGraphInstantiate(&m->bgraph_exec, m->bgraph, nullptr, nullptr, 0));
+        m->bgraph_B = B;
+    }
+    HH(hipGraphLaunch(m->bgraph_exec, m->st));
+    return 0;
+}
+// the host's counters follow the device state of sequences 0 .. B-1 (after a batch_generate, and after a failure inside its loop: resync_after_error's batched form)
+static int batch_read_state(M *m, int B, std::vector<SeqKV> &desc) {
+    desc.resize(B);
+    HH(hipStreamSynchronize(m->st));
+    HH(hipMemcpy(desc.data(), m->seqkv_dev, (size_t)B * sizeof(SeqKV), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+        const int grew = desc[b].t - m->seqs[b].cache_len;
+        if (grew < 0 || desc[b].t > m->c.cache_limit) continue;
+        m->seqs[b].cache_len = desc[b].t;
+        m->seqs[b].last_pos += (float)grew;
+    }
+    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+    return 0;
+}
+extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out,
+                                             float *elapsed_ms) {
+    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0) return MLLM_HIP_ERR_ARG;
+    EH(batch_check(m, B, steps, "mllm_hip_model_batch_generate"));
+    constexpr int EOS_CHECK_EVERY = 16;      // steps between two reads of BatchCtl::n_active (4 bytes, one synchronisation); a stopped batch overruns by fewer steps, which change nothing
+    EH(batch_upload_state(m, B, first_tokens, eos));
+    auto run = [&]() -> int {
+        HH(hipEventRecord(m->ev0, m->st));
+        for (int s = 0; s < steps; ++s) {
+            EH(batch_step(m, B));
+            if (eos >= 0 && (s + 1) % EOS_CHECK_EVERY == 0 && s + 1 < steps) {
+                int live = 0;
+                HH(hipStreamSynchronize(m->st));
+                HH(hipMemcpy(&live, &m->bctl->n_active, 4, hipMemcpyDeviceToHost));
+                if (live == 0) break;
+            }
+        }
+        HH(hipEventRecord(m->ev1, m->st));
+        return 0;
+    };
+    const int rc = run();
+    std::vector<SeqKV> desc;
+    const int rc2 = batch_read_state(m, B, desc);
+    if (rc) return rc;
+    EH(rc2);
+    if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
+    if (n_out) for (int b = 0; b < B; ++b) n_out[b] = desc[b].made;
+    if (tokens_host) {
+        HH(hipMemcpy2D(tokens_host, (size_t)steps * 4, m->bhist, (size_t)m->c.cache_limit * 4, (size_t)steps * 4, B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) for (int s = desc[b].made; s < steps; ++s) tokens_host[(size_t)b * steps + s] = -1;
+    }
     return MLLM_HIP_OK;
 }
 

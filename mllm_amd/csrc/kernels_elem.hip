@@ -608,7 +608,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float *__restrict__ 
 
 // first-maximum argmax of a row spread over the chip: workgroup b scans its slice and leaves (value, index); dec_next_kernel (decode) or argmax_final_kernel folds the
 // partials with the same tie rule (equal values: the smaller index).  The single-workgroup mllm_hip_argmax took 47 us on the 151,936 logits -- 7 % of a Qwen1.5-0.5B token.
-__global__ __launch_bounds__(256) void argmax_parts_kernel(const float *__restrict__ x, int n, float *__restrict__ part_val, int *__restrict__ part_idx) {
+__device__ __forceinline__ void argmax_slice(const float *__restrict__ x, int n, float *__restrict__ slot_val, int *__restrict__ slot_idx) {
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int per = (((n + (int)gridDim.x - 1) / (int)gridDim.x) + 3) & ~3;
@@ -626,8 +626,59 @@ __global__ __launch_bounds__(256) void argmax_parts_kernel(const float *__restri
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
-        part_val[blockIdx.x] = best;
-        part_idx[blockIdx.x] = besti;
+        *slot_val = best;
+        *slot_idx = besti;
+    }
+}
+__global__ __launch_bounds__(256) void argmax_parts_kernel(const float *__restrict__ x, int n, float *__restrict__ part_val, int *__restrict__ part_idx) {
+    argmax_slice(x, n, part_val + blockIdx.x, part_idx + blockIdx.x);
+}
+// the same over B rows in one launch (batched step): blockIdx.y = row, its partials at [row][gridDim.x]
+__global__ __launch_bounds__(256) void argmax_parts_rows_kernel(const float *__restrict__ x, int64_t ldx, int n, float *__restrict__ part_val, int *__restrict__ part_idx) {
+    const int64_t slot = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    argmax_slice(x + (int64_t)blockIdx.y * ldx, n, part_val + slot, part_idx + slot);
+}
+// The batched counterpart of dec_next_kernel: wave w folds row w's partial maxima (std::max_element: first maximum), records the id and advances that sequence's state in
+// device memory.  A stopped row keeps everything it has; a row that produces the end-of-sequence id keeps that id, counts the step and stops.  One workgroup, B <= 16 waves.
+__global__ __launch_bounds__(1024) void seqs_next_kernel(SeqKV *__restrict__ seqs, BatchCtl *__restrict__ ctl, const float *__restrict__ part_val, const int *__restrict__ part_idx,
+                                                         int nparts, int B, int *__restrict__ tok_out, float *__restrict__ ids_f, int *__restrict__ history, int hist_ld) {
+    __shared__ int live[16];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w < B) {
+        float best = -INFINITY;
+        int besti = 0x7fffffff;
+        for (int i = lane; i < nparts; i += 64) {
+            const float v = part_val[(int64_t)w * nparts + i];
+            const int ix = part_idx[(int64_t)w * nparts + i];
+            if (v > best || (v == best && ix < besti)) { best = v; besti = ix; }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(best, m, 64);
+            const int oi = __shfl_xor(besti, m, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if (lane == 0) {
+            int on = seqs[w].active;
+            if (on) {
+                const int made = seqs[w].made;
+                tok_out[w] = besti;
+                if (made < hist_ld) history[(int64_t)w * hist_ld + made] = besti;
+                ids_f[w] = (float)besti;      // the embedding reads fp32 ids (ids below 2^24 are exact)
+                if (besti == ctl->eos) on = 0;      // eos < 0 matches no id
+                seqs[w].t += 1;
+                seqs[w].pos += 1;
+                seqs[w].made = made + 1;
+                seqs[w].active = on;
+            }
+            live[w] = on;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int b = 0; b < B; ++b) n += live[b];
+        ctl->n_active = n;
     }
 }
 __global__ __launch_bounds__(64) void argmax_final_kernel(const float *__restrict__ part_val, const int *__restrict__ part_idx, int nparts, int *__restrict__ out) {
@@ -795,14 +846,18 @@ __global__ __launch_bounds__(256) void rope2_store2_kernel(const float *__restri
         }
     }
 }
-// the same for B sequences that each append ONE token to their own slabs (batched decode): row b of qkv, rotary row b, destination = sequence b's slabs at its position t_b
+// the same for B sequences that each append ONE token to their own slabs (batched step): row b of qkv, destination = sequence b's slabs at its position t_b, rotary row =
+// row pos_b of the resident table -- both read from the sequence's state in device memory, so a captured step needs no host between steps.  A stopped sequence writes
+// nothing (its row of the step is computed and dropped), and neither does one whose cache is full: row `cap` of a layer is row 0 of the next layer's keys.
 __global__ __launch_bounds__(256) void seqs_rope_append_kernel(float *__restrict__ qkv, int64_t ldq, const float *__restrict__ sin_t, const float *__restrict__ cos_t, int ld_tab,
-                                                               const SeqKV *__restrict__ seqs, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldv, int Hq, int Hkv,
-                                                               int D) {
+                                                               int tab_rows, const SeqKV *__restrict__ seqs, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldv,
+                                                               int Hq, int Hkv, int D, int cap) {
     const int b = blockIdx.y, half = D >> 1;
     const SeqKV sq = seqs[b];
+    if (!sq.active || sq.t < 0 || sq.t >= cap) return;
     uint16_t *kout = sq.k + layer_k_off + (int64_t)sq.t * ldk, *vout = sq.v + layer_v_off + sq.t;
     float *row = qkv + (int64_t)b * ldq;
+    const int64_t tab = (int64_t)min(max(sq.pos, 0), tab_rows - 1) * ld_tab;
     const int nq = Hq * half, nk = Hkv * half, nv = Hkv * D;
     for (int t = blockIdx.x * 256 + threadIdx.x; t < nq + nk + nv; t += gridDim.x * 256) {
         if (t < nq + nk) {
@@ -811,7 +866,7 @@ __global__ __launch_bounds__(256) void seqs_rope_append_kernel(float *__restrict
             const int d = u % half, h = u / half;
             float *x = row + (isk ? Hq * D : 0) + h * D + d;
             const float a = x[0], bb = x[half];
-            const float sv = sin_t[(int64_t)b * ld_tab + d], cv = cos_t[(int64_t)b * ld_tab + d];
+            const float sv = sin_t[tab + d], cv = cos_t[tab + d];
             const float v1 = __fmaf_rn(a, cv, -__fmul_rn(bb, sv)), v2 = __fmaf_rn(a, sv, __fmul_rn(bb, cv));
             if (isk) { uint16_t *o = kout + h * D + d; o[0] = f2h(v1); o[half] = f2h(v2); }
             else { x[0] = v1; x[half] = v2; }
@@ -1216,13 +1271,22 @@ extern "C" int mllm_hip_qkv_rope_append(float *qkv, int64_t ldq, const float *si
     return MH_LAUNCH_OK("qkv_rope_append");
 }
 namespace mllm_hip {
-int seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, const SeqKV *seqs_dev, int64_t layer_k_off, int64_t layer_v_off,
-                            int64_t ldk, int64_t ldvt, int B, int Hq, int Hkv, int D, hipStream_t st) {
+int seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, int tab_rows, const SeqKV *seqs_dev, int64_t layer_k_off,
+                            int64_t layer_v_off, int64_t ldk, int64_t ldvt, int B, int Hq, int Hkv, int D, int cap, hipStream_t st) {
     if (B <= 0) return MLLM_HIP_OK;
-    if (D % 2 || !qkv || !seqs_dev) return MLLM_HIP_ERR_ARG;
+    if (D % 2 || !qkv || !seqs_dev || !sin_t || !cos_t || tab_rows <= 0 || cap <= 0) return MLLM_HIP_ERR_ARG;
     const int n = (Hq + Hkv) * (D / 2) + Hkv * D;
-    hipLaunchKernelGGL(seqs_rope_append_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, qkv, ldq, sin_t, cos_t, ld_tab, seqs_dev, layer_k_off, layer_v_off, ldk, ldvt, Hq, Hkv, D);
+    hipLaunchKernelGGL(seqs_rope_append_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, qkv, ldq, sin_t, cos_t, ld_tab, tab_rows, seqs_dev, layer_k_off, layer_v_off, ldk, ldvt,
+                       Hq, Hkv, D, cap);
     return MH_LAUNCH_OK("seqs_rope_append");
+}
+int seqs_argmax_next_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, SeqKV *seqs_dev, BatchCtl *ctl, int *tok_out,
+                            float *ids_f, int *history, int hist_ld, hipStream_t st) {
+    if (!logits || !part_val || !part_idx || !seqs_dev || !ctl || !tok_out || !ids_f || !history || B < 1 || B > 16 || nparts < 1 || vocab < 1 || hist_ld < 1) return MLLM_HIP_ERR_ARG;
+    hipLaunchKernelGGL(argmax_parts_rows_kernel, dim3(nparts, B), dim3(256), 0, st, logits, ld_logits, vocab, part_val, part_idx);
+    if (int rc = MH_LAUNCH_OK("argmax_parts_rows")) return rc;
+    hipLaunchKernelGGL(seqs_next_kernel, dim3(1), dim3(1024), 0, st, seqs_dev, ctl, part_val, part_idx, nparts, B, tok_out, ids_f, history, hist_ld);
+    return MH_LAUNCH_OK("seqs_next");
 }
 }  // namespace mllm_hip
 extern "C" int mllm_hip_store_f16(const float *x, int64_t ldx, uint16_t *out, int64_t ldo, int S, int n, void *stream) {
@@ -1300,6 +1364,14 @@ extern "C" int mllm_hip_mrope_table(float base, int dim, const float *pos, int S
         c0 += section[j];
     }
     return MLLM_HIP_OK;
+}
+// The rotary rows of the decode steps as ONE table [n_pos][dim/2]: in decode all three M-RoPE axes hold the same position (modeling_qwen2_vl.hpp:423-432), so the row is a
+// function of that one integer; row p = mllm_hip_mrope_table's row for position p on every axis (tests/test_batch_generate_host.py pins the bits).
+extern "C" int mllm_hip_mrope_decode_table(float base, int dim, int n_pos, const int *section, int n_section, float *sin_host, float *cos_host) {
+    if (dim <= 0 || dim % 2 || n_pos <= 0 || !section || n_section <= 0 || !sin_host || !cos_host) return MLLM_HIP_ERR_ARG;
+    std::vector<float> pos((size_t)3 * n_pos);
+    for (int a = 0; a < 3; ++a) for (int p = 0; p < n_pos; ++p) pos[(size_t)a * n_pos + p] = (float)p;
+    return mllm_hip_mrope_table(base, dim, pos.data(), n_pos, section, n_section, sin_host, cos_host);
 }
 // VISIONROPE's output (CPUVisionRoPE.cpp:19-28 inv_freq by float pow, :56-103 (h, w) per patch in merge-block order, :29-55 angle = pos * inv_freq): the angle
 // table `[t*h*w][rot_dim]`, h angles in columns [0, rot_dim/2), w angles behind them

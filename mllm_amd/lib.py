@@ -150,6 +150,15 @@ def mrope_table(base, dim, pos, section=(16, 24, 24)):
     return s, c
 
 
+def mrope_decode_table(base, dim, n_pos, section=(16, 24, 24)):
+    """The resident rotary table of the batched step: row p = the M-RoPE row of position p on all three axes, [n_pos][dim / 2]."""
+    sec = np.asarray(section, dtype=np.int32)
+    s = np.zeros((n_pos, dim // 2), dtype=np.float32)
+    c = np.zeros((n_pos, dim // 2), dtype=np.float32)
+    check(load().mllm_hip_mrope_decode_table(C.c_float(base), C.c_int(dim), C.c_int(n_pos), vp(sec), C.c_int(len(sec)), vp(s), vp(c)), "mrope_decode_table")
+    return s, c
+
+
 def vision_rope_table(t, h, w, merge, rot_dim):
     s = np.empty((t * h * w, rot_dim), dtype=np.float32)
     c = np.empty((t * h * w, rot_dim), dtype=np.float32)
@@ -241,6 +250,17 @@ class Model:
         ms = C.c_float()
         check(load().mllm_hip_model_batch_decode(self._h, C.c_int(B), vp(t), vp(lg), vp(nxt), C.byref(ms)), "batch_decode")
         return nxt, lg, ms.value
+
+    def batch_generate(self, first_tokens, steps, eos=-1):
+        """Greedy generation for sequences 0 .. len(first_tokens) - 1 together, resident on the device (one captured step per B): (ids int32 [B][steps], n_out int32 [B],
+        device ms).  eos >= 0: a row that produces it stops there (n_out[b] = its steps, the rest of the row -1)."""
+        t = np.ascontiguousarray(first_tokens, dtype=np.int32)
+        B = int(t.size)
+        toks = np.empty((B, max(int(steps), 0)), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        ms = C.c_float()
+        check(load().mllm_hip_model_batch_generate(self._h, C.c_int(B), vp(t), C.c_int(int(steps)), C.c_int32(int(eos)), vp(toks), vp(n), C.byref(ms)), "batch_generate")
+        return toks, n, ms.value
 
     def cache_len(self) -> int:
         """Tokens the KV cache holds (0 on a fresh or cleared model)."""
