@@ -1895,6 +1895,8 @@ static size_t attn_pipe_lds(int D, int ds, int cache_limit) {
     return ds == 1 ? PIPE_LDS(64, 1) : (ds == 2 ? PIPE_LDS(64, 2) : PIPE_LDS(64, 4));
 #undef PIPE_LDS
 }
+// dynamic LDS of the fused tied head (dec_head_kernel): the normalised row, its Q8_0 form, and the Q4_0 dot tables of the workgroup's four waves
+static size_t dec_head_lds_bytes(int H) { return (((size_t)H * 5 + (size_t)H / 32 * 4 + 15) & ~(size_t)15) + 4 * q40_tab_floats(H / 32) * sizeof(float); }
 // workgroups of the roles of the shared launches (eight-wave workgroups; q|k|v: two rows per wave)
 static int qkv_role_grid(int qkv_N) { return ((qkv_N + 1) / 2 + 7) / 8; }
 static int oproj_role_grid(int N, int rows) { return ((N + rows - 1) / rows + 7) / 8; }
@@ -2012,7 +2014,8 @@ void decode_step_plan(const DecodeCtx &c, const DecodeLayer *layers, int n_layer
     head.kind = STEP_HEAD;
     next.kind = STEP_NEXT;
     if (c.Whead) head.persist = norm_gemv_walk(p, c.H, c.vocab, false);      // Linear lm_head (LLaMA-style models): the q|k|v projection's kernel
-    else if (c.H % 512 != 0 || c.H / 512 > 8) head.head = 1;                  // tied head on shapes the fused head kernel does not cover: the stand-alone launchers
+    // tied head on shapes the fused head kernel does not cover (its row + four waves' tables must fit the LDS: H / 512 <= 7): the stand-alone launchers
+    else if (c.H % 512 != 0 || c.H / 512 > 8 || dec_head_lds_bytes(c.H) > (size_t)160 * 1024) head.head = 1;
     else {                                                                    // tied head + partial argmax in one kernel, the rows split for head_wpc waves per CU
         head.head = 2;
         head.rows = ((c.vocab + 256 * p.head_wpc - 1) / (256 * p.head_wpc) + 7) / 8 * 8;
@@ -2178,7 +2181,7 @@ int decode_launch(const DecodeCtx &c, const StepPlan &p, const DecodeLayer *laye
         }
         {
             if (e.parts > c.max_parts) return MLLM_HIP_ERR_SHAPE;
-            const size_t lds = (((size_t)c.H * 5 + (size_t)c.H / 32 * 4 + 15) & ~(size_t)15) + 4 * q40_tab_floats(c.H / 32) * sizeof(float);
+            const size_t lds = dec_head_lds_bytes(c.H);
 #define HEAD_CASE(B) case B: rc = allow_lds(dec_head_kernel<B>, lds); if (rc) return rc; hipLaunchKernelGGL((dec_head_kernel<B>), dim3(e.parts), dim3(256), lds, st, x, c.final_norm, c.final_eps, c.emb_qs, c.emb_d, c.logits, c.part_val, c.part_idx, c.vocab, c.H, e.rows); break;
             switch (c.H / 512) { HEAD_CASE(1) HEAD_CASE(2) HEAD_CASE(3) HEAD_CASE(4) HEAD_CASE(5) HEAD_CASE(6) HEAD_CASE(7) HEAD_CASE(8) }
 #undef HEAD_CASE

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void gemv_q4k_kernel(const uint8_t *__restrict
             const int rw = min(row + rr, row1 - 1);
 #pragma unroll
             for (int st = 0; st < NSTEPS; ++st) {
-                const int blk = A.valid[st] ? st * 8 + g : 0;
+                const int blk = st * 8 + g < nb ? st * 8 + g : 0;      // (not A.valid[st]: with M > 1 the activation planes are only loaded inside the m loop)
                 const uint8_t *wb = W + ((int64_t)rw * nb + blk) * 144;
                 hdr[rr][st] = *reinterpret_cast<const uint4 *>(wb);
                 q[rr][st] = *reinterpret_cast<const uint4 *>(wb + 16 + qoff);
@@ -986,10 +986,13 @@ extern "C" int mllm_hip_linear_q4k_q8k(const void *W, const float *bias, const i
 extern "C" int mllm_hip_linear_q40_q80(const uint8_t *Wqs, const uint16_t *Wd, const float *bias, const int8_t *xqs, const uint16_t *xd,
                                        float *y, int64_t ldy, int M, int N, int K, void *stream) {
     if (K % 256 != 0 || K <= 0 || N <= 0) return MLLM_HIP_ERR_SHAPE;
-    // 16 lanes per row when K is a multiple of 512 (<= 8 blocks per lane), else 8 lanes per row (K multiple of 256)
+    // 16 lanes per row when K is a multiple of 512 (<= 8 blocks per lane), else 8 lanes per row (K an odd multiple of 256: 1, 3, .. 15 blocks per lane) -- every K <= 4096
     const int lpr = (K % 512 == 0 && K / 512 <= 8) ? 16 : 8;
     const int bpl = K / 32 / lpr;
-    if (bpl > 8) return MLLM_HIP_ERR_SHAPE;
+    if (bpl > (lpr == 16 ? 8 : 15) || (lpr == 8 && bpl % 2 == 0)) {
+        set_error_msg("mllm_hip_linear_q40_q80: rows of K = %d values are not covered (multiples of 256 up to 4096 are)", K);
+        return MLLM_HIP_ERR_SHAPE;
+    }
     hipStream_t st = as_stream(stream);
     const int target_waves = 256 * 8, rpp = 8;
     const size_t lds = 4 * q40_tab_floats(K / 32) * sizeof(float);
@@ -1004,7 +1007,7 @@ extern "C" int mllm_hip_linear_q40_q80(const uint8_t *Wqs, const uint16_t *Wd, c
         float *ym = y + (int64_t)m0 * ldy;
 #define Q40_CASE(B, L) if (bpl == B && lpr == L) hipLaunchKernelGGL((gemv_q40_kernel<B, L>), dim3((waves + 3) / 4), dim3(256), lds, st, Wqs, Wd, bias, xq, xdd, ym, N, rows_per_wave, mc, ldy);
         Q40_CASE(1, 16) Q40_CASE(2, 16) Q40_CASE(3, 16) Q40_CASE(4, 16) Q40_CASE(5, 16) Q40_CASE(6, 16) Q40_CASE(7, 16) Q40_CASE(8, 16)
-        Q40_CASE(1, 8) Q40_CASE(3, 8) Q40_CASE(5, 8) Q40_CASE(7, 8)
+        Q40_CASE(1, 8) Q40_CASE(3, 8) Q40_CASE(5, 8) Q40_CASE(7, 8) Q40_CASE(9, 8) Q40_CASE(11, 8) Q40_CASE(13, 8) Q40_CASE(15, 8)
 #undef Q40_CASE
         int rc = MH_LAUNCH_OK("gemv_q40");
         if (rc) return rc;

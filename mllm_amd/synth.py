@@ -319,8 +319,64 @@ def causal_lm_tensors(c: CausalLMConfig) -> Iterator[Tuple[str, Tuple[int, ...],
         yield "lm_head.weight", (c.vocab, H), "w"
 
 
-def causal_lm_ids(c: CausalLMConfig, n: int) -> np.ndarray:
-    return np.random.default_rng(13).integers(0, c.vocab, size=n).astype(np.int32)
+def causal_lm_ids(c: CausalLMConfig, n: int, seed: int = 13) -> np.ndarray:
+    return np.random.default_rng(seed).integers(0, c.vocab, size=n).astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the step-plan geometries: causal LMs whose shapes sit at, or just across, one edge of a shape predicate of decode_step_plan (csrc/kernels_decode.hip).  The reference's
+# runs on their full-range files are tests/golden/step_plan_<id>.npz (oracle/make_golden.py --step-plan); tests/test_step_plan_shapes.py (CPU) and
+# tests/test_gpu_step_plan_shapes.py replay them, and DESIGN.md "Step-plan geometries" lists which geometry pins which edge and the plan each one gets.
+#
+# Outcomes of the predicates that no CausalLMConfig / Qwen2VLConfig reaches (head_dim = hidden / heads, every Linear K a multiple of 256), so no geometry pins them:
+#   - merges_front's "q|k|v role grid % 8": the grid is (heads + 2 kv_heads) * D / 16 workgroups; D = 128 makes it a multiple of 8, and D = 64 needs an odd `heads`,
+#     which merges_o's heads * D % 256 == 0 has already turned away.
+#   - merges_chain's "down grid % 8": merges_front holds H <= 2048 and H % 256 == 0, pjb_serves at most 40 super-blocks per row, so a workgroup takes H / 256 rows
+#     and the grid is 256 workgroups, always.
+#   - merges_o's "heads * D % 256" and pjb_serves' "N >= rows per workgroup": hidden = heads * D is a multiple of 256 and at least 256.
+#   - the LDS-fit tests of the shared launches: with cache_limit <= 2048 and rows of at most 40 super-blocks the largest role stays below 110 KiB of the 160.
+# ---------------------------------------------------------------------------------------------------------------
+STEP_PLAN_PROMPT, STEP_PLAN_STEPS = 20, 24
+STEP_PLAN_LOGIT_STEPS = (0, 1, 2, 3, 7, 11, 15, 19, 23)      # the steps whose whole logit row the goldens keep: the prefill, three decode steps, every fourth, the last
+
+
+def _sp(family, hidden, inter, heads, kv_heads, vocab, layers=3):
+    qwen = family == "qwen"
+    return CausalLMConfig(family=family, hidden=hidden, inter=inter, layers=layers, heads=heads, kv_heads=kv_heads, vocab=vocab, rope_theta=1000000.0 if qwen else 10000.0,
+                          cache_limit=96, tie_embedding=qwen)
+
+
+STEP_PLAN_GEOMETRIES = {
+    # heads * D = H = 2048, the upper bound of merges_o and merges_front; q|k|v role grid 384 > the down grid of 256: chain launch with the role on its own workgroups
+    # (cont = 0); K/V group size 1 on 16 K/V heads (no cache warm); fused tied head at H / 512 = 4
+    "A": lambda: _sp("qwen", 2048, 5632, 16, 16, 2048),
+    # down rows of 17 super-blocks, the lower end of pjb_serves (NS = 3); I % 5 != 0: the eight-lane gate|up in front of a chain launch; one K/V head (group size 4);
+    # fused tied head at H / 512 = 1 on a vocabulary that is no multiple of its 8 rows per wave
+    "B": lambda: _sp("qwen", 512, 4352, 4, 1, 2043),
+    # down rows of 40 super-blocks, the upper end of pjb_serves (NS = 5); dec_gateup_blk at 5 super-blocks per row; 5 K/V heads of group size 2; Linear head, a workgroup
+    # per row group.  (10 / 2 heads and a vocabulary of 2048 collapse onto one id under every prompt tried; 10 / 5 and 1024 do not)
+    "C": lambda: _sp("tinyllama", 1280, 10240, 10, 5, 1024),
+    # 41 super-blocks, one past pjb_serves: the eight-lane down projection (NS = 6) as its own launch behind front launches; I % 5 != 0 at H / 256 = 6; tied head at H / 512 = 3
+    "D": lambda: _sp("qwen", 1536, 10496, 12, 2, 2048),
+    # D = 64 on 7 K/V heads of group size 4; H / 256 = 7, one past gub_serves (70 > 64): the eight-lane gate|up; H % 512 != 0: the tied head on the stand-alone
+    # launchers (form 1).  (28 / 4 heads, group size 7, stays below 8 distinct ids under every prompt tried)
+    "E": lambda: _sp("qwen", 1792, 4864, 28, 7, 2048),
+    # the first H past merges_o: five launches per layer with the two-step register forms (NS = 2), the persistent gate|up, the lane-per-super-block down projection
+    # (25 super-blocks) as a launch of its own; group size 9
+    "F": lambda: _sp("qwen", 2304, 6400, 18, 2, 2048),
+    # tied head at H / 512 = 8, ragged vocabulary: the shape test of the fused head admits it, its LDS (170,496 bytes) does not fit, so the plan takes the stand-alone
+    # launchers -- the fused head ends at H / 512 = 7; 8 K/V heads, the last count with the cache warm on; walking q|k|v (768 workgroups, NS = 2)
+    "G": lambda: _sp("qwen", 4096, 4096, 32, 8, 2043, layers=2),
+    # Linear head of 16391 rows: 1025 workgroups, one past the 1024 from which it walks, the last of them ragged (four of eight waves, the last with one row of two);
+    # front launches (down rows of 5 super-blocks: no chain) and dec_gateup_blk at 2 super-blocks per row
+    "H": lambda: _sp("tinyllama", 512, 1280, 4, 2, 16391),
+}
+# seed of each geometry's 20-id prompt (causal_lm_ids): 13 unless the reference's run on it misses the goldens' non-degeneracy bar (>= 8 distinct ids, >= 12 changes)
+STEP_PLAN_PROMPT_SEED = {"A": 17, "B": 14, "C": 23, "D": 27, "E": 35, "F": 18, "G": 13, "H": 13}
+
+
+def step_plan_geometry(gid: str) -> CausalLMConfig:
+    return STEP_PLAN_GEOMETRIES[gid]()
 
 
 @dataclass

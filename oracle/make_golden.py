@@ -6,6 +6,7 @@ oracle/Makefile.ref from /root/reference).  Runs only in the development contain
     make -f oracle/Makefile.ref -j8 && python oracle/make_golden.py [--full]          # op goldens + tiny Qwen2-VL (+ the 2 B runs)
     python oracle/make_golden.py --all [--full]                                          # every golden that depends on a synthetic model file
     python oracle/make_golden.py --informative                                           # the goldens on the full-range toy files (ids that change)
+    python oracle/make_golden.py --step-plan [ids]                                       # the runs on the step-plan geometries (synth.STEP_PLAN_GEOMETRIES)
     python oracle/make_golden.py --full-long                                             # the 2 B runs that decode past T = 512
 
 Op-level cases store their inputs (fp32), the raw weight bytes the reference consumed (written by the reference's own `quantize` tool from seeded fp32 arrays)
@@ -317,9 +318,9 @@ def e2e_full_long():
     print("qwen2vl_2b_ref_long.npz", _id_stats(toks), toks[:8], steps, timing)
 
 
-def run_ref_llm(c, n_prompt, steps, threads=4, full_range=False):
+def run_ref_llm(c, n_prompt, steps, threads=4, full_range=False, seed=13):
     td, path = tempfile.mkdtemp(dir=os.environ.get("MLLM_GOLD_TMP")), weights.causal_lm_file(c, CACHE, full_range=full_range)
-    ids = synth.causal_lm_ids(c, n_prompt)
+    ids = synth.causal_lm_ids(c, n_prompt, seed)
     ids.tofile(os.path.join(td, "ids.i32"))
     cfg = f"{c.hidden},{c.inter},{c.layers},{c.heads},{c.kv_heads},{c.vocab},{c.cache_limit},{int(c.tie_embedding)}"
     out = subprocess.run([os.path.join(REF, "ref_llm"), "--family", c.family, "--model", path, "--ids", os.path.join(td, "ids.i32"), "--steps", str(steps),
@@ -408,6 +409,28 @@ def informative_tiny():
     savez_stable(os.path.join(GOLD, "configs_tiny_fr.npz"), **G)
     for f in ("qwen2vl_tiny_fr.npz", "configs_tiny_fr.npz"):
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")
+
+
+def step_plan_goldens(only=None):
+    """step_plan_<id>.npz, one per geometry of synth.STEP_PLAN_GEOMETRIES (shapes at the edges of decode_step_plan's predicates): the reference's run on the full-range
+    file, a 20-id prompt + 24 greedy steps.  Every greedy id; the whole logit row of synth.STEP_PLAN_LOGIT_STEPS (`steps`); where the vocabulary is large (H) also the
+    sampled form of every step (top-64 ids and values, every 97th logit).  Every run clears nondegenerate(); every file stays under 1,000,000 bytes."""
+    keep = list(synth.STEP_PLAN_LOGIT_STEPS)
+    for gid in synth.STEP_PLAN_GEOMETRIES:
+        if only and gid not in only:
+            continue
+        c = synth.step_plan_geometry(gid)
+        threads = max(t for t in range(1, 9) if c.heads % t == 0)      # FA2 asserts heads % threads == 0 (FlashAttention2.hpp:128)
+        ids, toks, lg, _ = run_ref_llm(c, synth.STEP_PLAN_PROMPT, synth.STEP_PLAN_STEPS, threads=threads, full_range=True, seed=synth.STEP_PLAN_PROMPT_SEED[gid])
+        print(f"step_plan_{gid}.npz", _id_stats(toks), toks[:12].tolist())
+        assert nondegenerate(toks), (gid, toks.tolist())
+        out = {"ids": ids, "tokens": toks, "steps": np.array(keep, dtype=np.int32), "logits": lg[keep]}
+        if c.vocab > 4096:
+            out["top_idx"], out["top_val"], out["strided"] = _sampled(lg)
+        path = os.path.join(GOLD, f"step_plan_{gid}.npz")
+        savez_stable(path, **out)
+        assert os.path.getsize(path) <= 1_000_000, (gid, os.path.getsize(path))
+        print(f"step_plan_{gid}.npz", os.path.getsize(path) // 1024, "KiB")
 
 
 def run_ref_vit(c, n_img, threads=4):
@@ -716,6 +739,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--informative" in sys.argv:
         informative_tiny()
+        sys.exit(0)
+    if "--step-plan" in sys.argv:      # optionally followed by geometry ids: --step-plan A E
+        step_plan_goldens([a for a in sys.argv[sys.argv.index("--step-plan") + 1:] if a in synth.STEP_PLAN_GEOMETRIES])
         sys.exit(0)
     if "--all" in sys.argv:      # every golden that depends on a synthetic model file
         e2e_tiny()
