@@ -360,11 +360,13 @@ __global__ __launch_bounds__(NT) void fa2_decode_step_kernel(const AttnStep A) {
     const DecodeLds L = carve_decode(fa_smem, cap, D, NT, A.nslots);
     const bool writer = head == kvh * gsize;
     if (tid < HALF) {
-        const float v1 = __fmaf_rn(qa, cs, -__fmul_rn(qb, sn)), v2 = __fmaf_rn(qa, sn, __fmul_rn(qb, cs));
+        float v1, v2;
+        rope_pair(qa, qb, sn, cs, v1, v2);
         L.qs[tid] = v1; L.qs[tid + HALF] = v2;
         A.q_out[head * D + tid] = v1; A.q_out[head * D + tid + HALF] = v2;
     } else if (tid < D) {
-        const float v1 = __fmaf_rn(qa, cs, -__fmul_rn(qb, sn)), v2 = __fmaf_rn(qa, sn, __fmul_rn(qb, cs));
+        float v1, v2;
+        rope_pair(qa, qb, sn, cs, v1, v2);
         knew[tid - HALF] = f2h(v1); knew[tid] = f2h(v2);
         if (writer) { A.k_out[kvh * D + tid - HALF] = v1; A.k_out[kvh * D + tid] = v2; }
     } else if (tid < 2 * D) {

@@ -111,25 +111,6 @@ __device__ unsigned long long g_stamps[8192 * 16];
 #include "kernels_attn_core.h"
 namespace mllm_hip {
 
-__device__ __forceinline__ float v_expf_dec(float x) {  // same polynomial as kernels_elem.hip v_expf (mllm_v_expf)
-    const float r = 0x1.8p23f;
-    const float z = __fmaf_rn(x, 0x1.715476p+0f, r);
-    const float n = z - r;
-    const float b = __fmaf_rn(-n, 0x1.7f7d1cp-20f, __fmaf_rn(-n, 0x1.62e4p-1f, x));
-    const uint32_t e = __float_as_uint(z) << 23;
-    const float k = __uint_as_float(e + __float_as_uint(1.0f));
-    const bool c = fabsf(n) > 126.0f;
-    const float u = b * b;
-    const float j = __fmaf_rn(__fmaf_rn(__fmaf_rn(0x1.0e4020p-7f, b, 0x1.573e2ep-5f), u, __fmaf_rn(0x1.555e66p-3f, b, 0x1.fffdb6p-2f)), u,
-                              0x1.ffffecp-1f * b);
-    if (!c) return __fmaf_rn(j, k, k);
-    const uint32_t g = (n <= 0.0f) ? 0x82000000u : 0u;
-    const float s1 = __uint_as_float(g + 0x7f000000u);
-    const float s2 = __uint_as_float(e - g);
-    if (fabsf(n) > 192.0f) return s1 * s1;
-    return __fmaf_rn(s2, j, s2) * s1;
-}
-
 // ---- shared-memory image of one Q8_K quantised activation row ---------------------------------------------------------
 // layout in dynamic LDS (16-B aligned pieces): qs[K] | d[K/256] | q8s[K/32] (int32 sums of 32) ; xf[K] scratch (fp32)
 struct ActLds {
@@ -172,11 +153,7 @@ __device__ __forceinline__ void wave_quant_blocks_chain(const float4 (&v)[NB], i
 #pragma unroll
     for (int i = 0; i < NB; ++i) amax[i] = wave_max(amax[i]);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const float a0 = fabsf(v[i].x), a1 = fabsf(v[i].y), a2 = fabsf(v[i].z), a3 = fabsf(v[i].w);
-        const float mine = a0 == amax[i] ? v[i].x : (a1 == amax[i] ? v[i].y : (a2 == amax[i] ? v[i].z : v[i].w));
-        mx[i] = first_flagged(a0 == amax[i] || a1 == amax[i] || a2 == amax[i] || a3 == amax[i], mine);
-    }
+    for (int i = 0; i < NB; ++i) mx[i] = q8k_first_in_order(v[i], amax[i]);
     int qsum[NB];
     uint32_t packed[NB];
     float dd[NB];
@@ -209,37 +186,15 @@ __device__ __forceinline__ void wave_quant_blocks(const float4 (&v)[NB], int lan
     float hi[NB], lo[NB];
     unsigned abits[NB], mbits[NB];      // wave-uniform: bits of amax (>= +0) and of the signed first maximum
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        // v_max3 / v_min3 spelled out: fmaxf() on loaded values is preceded by a canonicalising v_max x, x per operand (IEEE mode)
-        float t;
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(t) : "v"(v[i].x), "v"(v[i].y), "v"(v[i].z));
-        asm("v_max_f32 %0, %1, %2" : "=v"(hi[i]) : "v"(t), "v"(v[i].w));
-        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(t) : "v"(v[i].x), "v"(v[i].y), "v"(v[i].z));
-        asm("v_min_f32 %0, %1, %2" : "=v"(lo[i]) : "v"(t), "v"(v[i].w));
-    }
+    for (int i = 0; i < NB; ++i) q8k_hi_lo(v[i], hi[i], lo[i]);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        float am;
-        asm("v_max_f32 %0, |%1|, |%2|" : "=v"(am) : "v"(hi[i]), "v"(lo[i]));
-        abits[i] = wave_umax(__float_as_uint(am));
-    }
+    for (int i = 0; i < NB; ++i) abits[i] = q8k_amax_bits(hi[i], lo[i]);
     bool tangled = false;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const float amax = __uint_as_float(abits[i]);
-        const unsigned long long pos = __ballot(hi[i] == amax), neg = __ballot(lo[i] == -amax);
-        const unsigned long long both = pos | neg, first = both & (0ull - both);
-        mbits[i] = abits[i] ^ ((neg & first) ? 0x80000000u : 0u);
-        tangled |= (pos & neg & first) != 0 && abits[i] != 0;
-    }
+    for (int i = 0; i < NB; ++i) tangled |= q8k_sign(hi[i], lo[i], abits[i], mbits[i]);
     if (tangled) {      // some lane holds +amax and -amax and is the first to hold either: the element order inside it decides
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const float amax = __uint_as_float(abits[i]);
-            const float a0 = fabsf(v[i].x), a1 = fabsf(v[i].y), a2 = fabsf(v[i].z), a3 = fabsf(v[i].w);
-            const float mine = a0 == amax ? v[i].x : (a1 == amax ? v[i].y : (a2 == amax ? v[i].z : v[i].w));
-            mbits[i] = __float_as_uint(first_flagged(a0 == amax || a1 == amax || a2 == amax || a3 == amax, mine));
-        }
+        for (int i = 0; i < NB; ++i) mbits[i] = __float_as_uint(q8k_first_in_order(v[i], __uint_as_float(abits[i])));
     }
     float isc[NB], dd[NB];
     if constexpr (NB >= 3) {
@@ -263,13 +218,10 @@ __device__ __forceinline__ void wave_quant_blocks(const float4 (&v)[NB], int lan
     uint32_t packed[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-        const f32x2_t s = {isc[i], isc[i]}, magic = {12582912.0f, 12582912.0f};
-        const f32x2_t m01 = f32x2_t{v[i].x, v[i].y} * s + magic, m23 = f32x2_t{v[i].z, v[i].w} * s + magic;      // -ffp-contract=off: a product, then a sum
-        const uint32_t top = 0x4B40007Fu;      // bits of 12582912 + 127
-        const uint32_t b0 = min(__float_as_uint(m01.x), top), b1 = min(__float_as_uint(m01.y), top);
-        const uint32_t b2 = min(__float_as_uint(m23.x), top), b3 = min(__float_as_uint(m23.y), top);
-        packed[i] = __builtin_amdgcn_perm(b1, b0, 0x0c0c0400u) | __builtin_amdgcn_perm(b3, b2, 0x04000c0cu);
-        qsum[i] = __builtin_amdgcn_sdot4((int)packed[i], 0x01010101, 0, false);
+        uint32_t b[4];
+        q8k_round4(v[i], isc[i], b);
+        packed[i] = q8k_bytes(b);
+        qsum[i] = q8k_sum4(packed[i]);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) qsum[i] = group8_sum(qsum[i]);   // 8 lanes = 32 values (bsums[2k] + bsums[2k+1])
@@ -331,13 +283,12 @@ __device__ __forceinline__ void wg_rmsnorm_quant(const float4 (&xv)[NV], const f
     ss = red[0];
 #pragma unroll
     for (int w = 1; w < WPB; ++w) ss += red[w];
-    const float m = (float)(ss / (double)dim);
-    const float inv = 1.0f / sqrtf(m + eps);
+    const float inv = rms_inv(ss, dim, eps);
     const int nblk = dim >> 8;
     float4 o[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        o[i].x = (xv[i].x * inv) * wv[i].x; o[i].y = (xv[i].y * inv) * wv[i].y; o[i].z = (xv[i].z * inv) * wv[i].z; o[i].w = (xv[i].w * inv) * wv[i].w;
+        o[i].x = rms_scale(xv[i].x, inv, wv[i].x); o[i].y = rms_scale(xv[i].y, inv, wv[i].y); o[i].z = rms_scale(xv[i].z, inv, wv[i].z); o[i].w = rms_scale(xv[i].w, inv, wv[i].w);
         if (norm_out && wid + WPB * i < nblk) *reinterpret_cast<float4 *>(norm_out + (wid + WPB * i) * 256 + lane * 4) = o[i];      // the RMSNORM Op's own output (adapter runs)
     }
     wave_quant_blocks<NV, WPB>(o, lane, wid, nblk, a);
@@ -433,10 +384,10 @@ __device__ __forceinline__ void dec_qkv_body(const DecodeState *__restrict__ sta
                 const float d = h2f(dd[blk]);
                 const uint32_t b4 = *reinterpret_cast<const uint32_t *>(q + blk * 16 + (jj & 15));
                 const int sh = jj >= 16 ? 4 : 0;
-                v.x = (float)((int)((b4 >> sh) & 0xF) - 8) * d;
-                v.y = (float)((int)((b4 >> (8 + sh)) & 0xF) - 8) * d;
-                v.z = (float)((int)((b4 >> (16 + sh)) & 0xF) - 8) * d;
-                v.w = (float)((int)((b4 >> (24 + sh)) & 0xF) - 8) * d;
+                v.x = q40_value((b4 >> sh) & 0xF, d);
+                v.y = q40_value((b4 >> (8 + sh)) & 0xF, d);
+                v.z = q40_value((b4 >> (16 + sh)) & 0xF, d);
+                v.w = q40_value((b4 >> (24 + sh)) & 0xF, d);
                 if (wg == 0) *reinterpret_cast<float4 *>(x_out + d0) = v;
             }
             xv[i] = v;
@@ -619,7 +570,7 @@ __global__ __launch_bounds__(64 * WPB) void dec_gateup_kernel(const float *__res
                 const int n = cur * PAIRS + p;
                 if (n < I) {
                     const float g = out[2 * p], u = out[2 * p + 1];
-                    act[n] = (g / (1.0f + v_expf_dec(0.0f - g))) * u;   // mllm_v_silu then F_TTMUL
+                    act[n] = ref_silu(g) * u;   // mllm_v_silu then F_TTMUL
                 }
             }
         }
@@ -843,13 +794,13 @@ __global__ __launch_bounds__(64 * WPB) void dec_gateup_blk_kernel(const float *_
     if (live && lane < PAIRS) {
         const float g = outv[2 * lane], u = outv[2 * lane + 1];
         if constexpr (ADAPT) {
-            const float sg = g / (1.0f + v_expf_dec(0.0f - g));
+            const float sg = ref_silu(g);
             E.g_out[p0 + lane] = g;      // in the Ops' order: the frontend may have handed the gate's block to the up projection's output
             if (E.silu_out) E.silu_out[p0 + lane] = sg;
             E.u_out[p0 + lane] = u;
             act[p0 + lane] = sg * u;
         } else
-        act[p0 + lane] = (g / (1.0f + v_expf_dec(0.0f - g))) * u;   // mllm_v_silu then F_TTMUL
+        act[p0 + lane] = ref_silu(g) * u;   // mllm_v_silu then F_TTMUL
     }
     GSTAMP(6);
 }
@@ -1073,11 +1024,12 @@ __global__ __launch_bounds__(DEC_ATTN_NT) void dec_attn_kernel(const DecodeState
     if (two_stage) fa2_decode_prefetch<D, true, DEC_ATTN_NT, true, DV>(P, kslab, KVD, vslab, vt_ld, kvh * D, cache_limit, nslots, 2, T);
     __builtin_amdgcn_sched_barrier(0);
     if (tid < HALF) {
-        L.qs[tid] = __fmaf_rn(qa, cs, -(qb * sn));
-        L.qs[tid + HALF] = __fmaf_rn(qa, sn, qb * cs);
+        rope_pair(qa, qb, sn, cs, L.qs[tid], L.qs[tid + HALF]);
     } else if (tid < D) {
-        knew[tid - HALF] = f2h(__fmaf_rn(qa, cs, -(qb * sn)));
-        knew[tid] = f2h(__fmaf_rn(qa, sn, qb * cs));
+        float v1, v2;
+        rope_pair(qa, qb, sn, cs, v1, v2);
+        knew[tid - HALF] = f2h(v1);
+        knew[tid] = f2h(v2);
     } else if (tid < 2 * D) {
         vnew[tid - D] = f2h(qa);
     }
@@ -1204,11 +1156,12 @@ __device__ __forceinline__ void dec_attn_pipe_body(const DecodeState *__restrict
         CSTAMP(2);
     }
     if (tid < HALF) {
-        L.qs[tid] = __fmaf_rn(qa, cs, -(qb * sn));
-        L.qs[tid + HALF] = __fmaf_rn(qa, sn, qb * cs);
+        rope_pair(qa, qb, sn, cs, L.qs[tid], L.qs[tid + HALF]);
     } else if (tid < D) {
-        knew[tid - HALF] = f2h(__fmaf_rn(qa, cs, -(qb * sn)));
-        knew[tid] = f2h(__fmaf_rn(qa, sn, qb * cs));
+        float v1, v2;
+        rope_pair(qa, qb, sn, cs, v1, v2);
+        knew[tid - HALF] = f2h(v1);
+        knew[tid] = f2h(v2);
     } else if (tid < 2 * D) {
         vnew[tid - D] = f2h(qa);
     }
@@ -1367,19 +1320,18 @@ __global__ __launch_bounds__(256) void dec_head_kernel(const float *__restrict__
     if (lane == 0) red[wid] = ss;
     __syncthreads();
     ss = red[0] + red[1] + red[2] + red[3];
-    const float inv = 1.0f / sqrtf((float)(ss / (double)K) + eps);
-    // Q8_0 (quantize_row_q8_0's AVX2 path, as quantize_q80_kernel): 8 lanes per 32-block
+    const float inv = rms_inv(ss, K, eps);
+    // Q8_0: 8 lanes per 32-block
     for (int blk = tid >> 3; blk < K / 32; blk += 32) {
         const int d4 = blk * 32 + (tid & 7) * 4;
         float4 v = *reinterpret_cast<const float4 *>(xf + d4);
         const float4 ww = *reinterpret_cast<const float4 *>(norm_w + d4);
-        v.x = (v.x * inv) * ww.x; v.y = (v.y * inv) * ww.y; v.z = (v.z * inv) * ww.z; v.w = (v.w * inv) * ww.w;
+        v.x = rms_scale(v.x, inv, ww.x); v.y = rms_scale(v.y, inv, ww.y); v.z = rms_scale(v.z, inv, ww.z); v.w = rms_scale(v.w, inv, ww.w);
         float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
         amax = group8_max(amax);
-        const float dd = amax / 127.0f;
-        const float id = amax != 0.0f ? 127.0f / amax : 0.0f;
-        const int a0 = (int)rintf(v.x * id), a1 = (int)rintf(v.y * id), a2 = (int)rintf(v.z * id), a3 = (int)rintf(v.w * id);
-        *reinterpret_cast<uint32_t *>(xq + d4) = (uint32_t)(a0 & 0xff) | ((uint32_t)(a1 & 0xff) << 8) | ((uint32_t)(a2 & 0xff) << 16) | ((uint32_t)(a3 & 0xff) << 24);
+        float dd, id;
+        q80_scale(amax, dd, id);
+        *reinterpret_cast<uint32_t *>(xq + d4) = q80_round4(v, id);
         if ((tid & 7) == 0) xdd[blk] = h2f(f2h(dd));
     }
     __syncthreads();
@@ -1424,16 +1376,11 @@ __global__ __launch_bounds__(256) void dec_head_kernel(const float *__restrict__
         }
     }
     // workgroup argmax with first-index tie break
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(besti, m, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    wave_first_max(best, besti);
     if (lane == 0) { bv[wid] = best; bi[wid] = besti; }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
+        fold_first_max<4>(bv, bi, best, besti);
         part_val[blockIdx.x] = best;
         part_idx[blockIdx.x] = besti;
     }
@@ -1456,18 +1403,13 @@ __global__ __launch_bounds__(256) void dec_next_kernel(DecodeState *__restrict__
     for (int i = threadIdx.x; i < nparts; i += 256) {
         const float v = part_val[i];
         const int ix = part_idx[i];
-        if (v > best || (v == best && ix < besti)) { best = v; besti = ix; }
+        first_max_merge(best, besti, v, ix);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(besti, m, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    wave_first_max(best, besti);
     if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
+        fold_first_max<4>(bv, bi, best, besti);
         *tok_out = besti;
         if (history) history[state->step] = besti;
         state->token = besti;
@@ -1621,7 +1563,7 @@ int dec_linear_row_q4k(const void *Wraw, const float *x, const float *addend, fl
 // The reference's frontend issues a decode layer one Op at a time: F_TTADD -> RMSNorm -> Linear q, k, v ... Linear o -> F_TTADD ... RMSNorm -> Linear gate -> SiLU -> Linear up ->
 // F_TTMUL -> Linear down -> F_TTADD.  This kernel is dec_proj_blk_kernel (one lane per super-block, rows by LDS-DMA) with the neighbouring Ops folded in, every Op's own output still
 // written (the frontend owns those tensors), every value computed by the arithmetic of the Op's own kernel:
-//   prologue   s = xa + xb (F_TTADD, CPUBinaryFunc.hpp)  ->  n = RMSNorm(s) (norm_kernel's double sum, (x * inv) * w)  ->  Q8_K of n   (each optional; workgroup 0 stores s and n)
+//   prologue   s = xa + xb (F_TTADD, CPUBinaryFunc.hpp)  ->  n = RMSNorm(s) (norm_kernel's double sum, rms_inv, rms_scale)  ->  Q8_K of n   (each optional; workgroup 0 stores s and n)
 //   body       up to three Linears on that row (q | k | v), each its own raw Q4_K rows + bias: y = dot + bias
 //   epilogue   mode 0: post_out = y + post_add (the F_TTADD behind an o / down projection);   mode 1: segment 0 = gate, 1 = up: silu_out = silu(y0), mul_out = silu_out * y1
 // A workgroup covers `rpw` consecutive rows of one segment (mode 1: rpw / 2 rows of the gate and the same rows of the up projection).
@@ -1695,7 +1637,7 @@ __global__ __launch_bounds__(64 * WPB) void row_fused_kernel(const RowFusedArgs 
         if (wid + WPB * i >= nb) v[i] = make_float4(0, 0, 0, 0);
         else if (A.sum_out && blockIdx.x == 0) *reinterpret_cast<float4 *>(A.sum_out + (wid + WPB * i) * 256 + lane * 4) = v[i];
     }
-    if (has_n) {      // norm_kernel<false>: double sum of squares, inv = 1 / sqrt(mean + eps), (x * inv) * w
+    if (has_n) {      // RMSNorm: double sum of squares, then rms_inv / rms_scale
         double ss = 0.0;
 #pragma unroll
         for (int i = 0; i < NQ; ++i) ss += (double)v[i].x * (double)v[i].x + (double)v[i].y * (double)v[i].y + (double)v[i].z * (double)v[i].z + (double)v[i].w * (double)v[i].w;
@@ -1705,12 +1647,10 @@ __global__ __launch_bounds__(64 * WPB) void row_fused_kernel(const RowFusedArgs 
         ss = red[0];
 #pragma unroll
         for (int w = 1; w < WPB; ++w) ss += red[w];
-        const float m = (float)(ss / (double)K);
-        const float inv = __fdiv_rn(1.0f, sqrtf(__fadd_rn(m, A.eps)));
+        const float inv = rms_inv(ss, K, A.eps);
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-            v[i].x = __fmul_rn(__fmul_rn(v[i].x, inv), wv[i].x); v[i].y = __fmul_rn(__fmul_rn(v[i].y, inv), wv[i].y);
-            v[i].z = __fmul_rn(__fmul_rn(v[i].z, inv), wv[i].z); v[i].w = __fmul_rn(__fmul_rn(v[i].w, inv), wv[i].w);
+            v[i].x = rms_scale(v[i].x, inv, wv[i].x); v[i].y = rms_scale(v[i].y, inv, wv[i].y); v[i].z = rms_scale(v[i].z, inv, wv[i].z); v[i].w = rms_scale(v[i].w, inv, wv[i].w);
             if (wid + WPB * i >= nb) v[i] = make_float4(0, 0, 0, 0);
             else if (A.norm_out && blockIdx.x == 0) *reinterpret_cast<float4 *>(A.norm_out + (wid + WPB * i) * 256 + lane * 4) = v[i];
         }
@@ -1753,7 +1693,7 @@ __global__ __launch_bounds__(64 * WPB) void row_fused_kernel(const RowFusedArgs 
         float g = resbuf[tid], u = resbuf[half + tid];
         if (A.seg[0].bias) g = __fadd_rn(g, A.seg[0].bias[rw]);
         if (A.seg[1].bias) u = __fadd_rn(u, A.seg[1].bias[rw]);
-        const float sg = __fdiv_rn(g, __fadd_rn(1.0f, v_expf_dec(__fsub_rn(0.0f, g))));      // silu_kernel's silu_ref
+        const float sg = ref_silu(g);
         A.seg[0].y[rw] = g;                 // in the Ops' order: the frontend may have handed the gate's block to the up projection's output
         if (A.silu_out) A.silu_out[rw] = sg;
         A.seg[1].y[rw] = u;

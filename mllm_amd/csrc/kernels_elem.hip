@@ -47,8 +47,8 @@ __device__ __forceinline__ void wave_quant_pack(float4 v, int lane, bool live, u
     const float iscale = nz ? __fdiv_rn(-128.0f, mx) : 0.0f, dd = nz ? __fdiv_rn(1.0f, iscale) : 0.0f;
     uint32_t b[4];
     q8k_round4(v, iscale, b);
-    const f32x2_t unmagic = {-12582912.0f, -12582912.0f};
-    const f32x2_t q01 = f32x2_t{__uint_as_float(b[0]), __uint_as_float(b[1])} + unmagic, q23 = f32x2_t{__uint_as_float(b[2]), __uint_as_float(b[3])} + unmagic;      // q as floats, exactly
+    f32x2_t q01, q23;
+    q8k_floats(b, q01, q23);
     const size_t tile = (size_t)(m >> 5) * nb + i;
     const int mi = m & 31, j = lane >> 4, hf = (lane >> 3) & 1, t = lane & 7;
     v4h_t o;
@@ -87,9 +87,7 @@ __global__ __launch_bounds__(256) void quantize_q8k_kernel(const float *__restri
     wave_quant_q8k(v, lane, qs + blk * 256, d + blk, bsums + blk * 16);
 }
 
-// quantize_row_q8_0 as the reference's x86 build runs it, the AVX2 path (ggml QuantizeQ8.cpp:113-167), not quantize_row_q8_0_reference:
-// d = amax/127 (stored fp16), q = rint(x * (127/amax)) -- _mm256_round_ps(_MM_ROUND_NEAREST) takes halves to even.
-// One lane per 32-block would serialise; use 8 lanes per block (4 values each), 8 blocks per wave.
+// quantize_row_q8_0 (q80_scale, q80_round4).  One lane per 32-block would serialise; use 8 lanes per block (4 values each), 8 blocks per wave.
 __global__ __launch_bounds__(256) void quantize_q80_kernel(const float *__restrict__ x, int8_t *__restrict__ qs, uint16_t *__restrict__ d, int64_t n_blocks) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -99,13 +97,10 @@ __global__ __launch_bounds__(256) void quantize_q80_kernel(const float *__restri
     if (ok) v = reinterpret_cast<const float4 *>(x + blk * 32)[lane & 7];
     float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     amax = group8_max(amax);
-    const float dd = __fdiv_rn(amax, 127.0f);
-    const float id = amax != 0.0f ? __fdiv_rn(127.0f, amax) : 0.0f;
+    float dd, id;
+    q80_scale(amax, dd, id);
     if (!ok) return;
-    const int q0 = (int)rintf(__fmul_rn(v.x, id)), q1 = (int)rintf(__fmul_rn(v.y, id));
-    const int q2 = (int)rintf(__fmul_rn(v.z, id)), q3 = (int)rintf(__fmul_rn(v.w, id));
-    const uint32_t packed = (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
-    reinterpret_cast<uint32_t *>(qs + blk * 32)[lane & 7] = packed;
+    reinterpret_cast<uint32_t *>(qs + blk * 32)[lane & 7] = q80_round4(v, id);
     if ((lane & 7) == 0) d[blk] = f2h(dd);
 }
 
@@ -218,8 +213,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const float *__restrict__ x, 
         if (lane == 0) red[wid] = ss;
         __syncthreads();
         ss = red[0] + red[1] + red[2] + red[3];
-        const float m = (float)(ss / (double)dim);
-        inv = __fdiv_rn(1.0f, sqrtf(__fadd_rn(m, eps)));
+        inv = rms_inv(ss, dim, eps);
     } else {
         mean = stats[2 * row];
         inv = stats[2 * row + 1];   // "rms" of the reference: the divisor
@@ -235,10 +229,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const float *__restrict__ x, 
             if (!LAYERNORM) {
                 const float w0 = add_unit_offset ? 1.0f + ww.x : ww.x, w1 = add_unit_offset ? 1.0f + ww.y : ww.y;
                 const float w2 = add_unit_offset ? 1.0f + ww.z : ww.z, w3 = add_unit_offset ? 1.0f + ww.w : ww.w;
-                o.x = __fmul_rn(__fmul_rn(v.x, inv), w0);
-                o.y = __fmul_rn(__fmul_rn(v.y, inv), w1);
-                o.z = __fmul_rn(__fmul_rn(v.z, inv), w2);
-                o.w = __fmul_rn(__fmul_rn(v.w, inv), w3);
+                o.x = rms_scale(v.x, inv, w0); o.y = rms_scale(v.y, inv, w1); o.z = rms_scale(v.z, inv, w2); o.w = rms_scale(v.w, inv, w3);
             } else {
                 float4 bb = make_float4(0, 0, 0, 0);
                 if (b) bb = *reinterpret_cast<const float4 *>(b + d0);
@@ -258,7 +249,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const float *__restrict__ x, 
     } else {
         for (int d = tid; d < dim; d += 256) {
             float o;
-            if (!LAYERNORM) o = __fmul_rn(__fmul_rn(xr[d], inv), add_unit_offset ? 1.0f + w[d] : w[d]);
+            if (!LAYERNORM) o = rms_scale(xr[d], inv, add_unit_offset ? 1.0f + w[d] : w[d]);
             else { o = __fdiv_rn(__fmul_rn(w[d], __fsub_rn(xr[d], mean)), inv); if (b) o = __fadd_rn(o, b[d]); }
             y[(int64_t)row * dim + d] = o;
         }
@@ -349,38 +340,17 @@ __global__ __launch_bounds__(64 * LNF_ROWS) void ln_fused_kernel(const float *__
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// A14: x/(1+exp(-x)) with the reference's AVX2 polynomial expf, one fp32 lane of it
-// (compute/ActivationFunction.hpp:96-134 mllm_v_expf, :137-146 mllm_v_silu): same constants, same fma placement.
+// A14: x/(1+exp(-x)) with the reference's AVX2 polynomial expf (ref_silu, ref_expf_poly)
 // ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float v_expf(float x) {
-    const float r = 0x1.8p23f;
-    const float z = __fmaf_rn(x, 0x1.715476p+0f, r);
-    const float n = __fsub_rn(z, r);
-    const float b = __fmaf_rn(-n, 0x1.7f7d1cp-20f, __fmaf_rn(-n, 0x1.62e4p-1f, x));
-    const uint32_t e = __float_as_uint(z) << 23;
-    const float k = __uint_as_float(e + __float_as_uint(1.0f));
-    const bool c = fabsf(n) > 126.0f;
-    const float u = __fmul_rn(b, b);
-    const float j = __fmaf_rn(__fmaf_rn(__fmaf_rn(0x1.0e4020p-7f, b, 0x1.573e2ep-5f), u, __fmaf_rn(0x1.555e66p-3f, b, 0x1.fffdb6p-2f)), u,
-                              __fmul_rn(0x1.ffffecp-1f, b));
-    if (!c) return __fmaf_rn(j, k, k);
-    const uint32_t g = (n <= 0.0f) ? 0x82000000u : 0u;
-    const float s1 = __uint_as_float(g + 0x7f000000u);
-    const float s2 = __uint_as_float(e - g);
-    if (fabsf(n) > 192.0f) return __fmul_rn(s1, s1);
-    return __fmul_rn(__fmaf_rn(s2, j, s2), s1);
-}
-__device__ __forceinline__ float silu_ref(float x) { return __fdiv_rn(x, __fadd_rn(1.0f, v_expf(__fsub_rn(0.0f, x)))); }
-
 __global__ __launch_bounds__(256) void silu_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t n) {
     int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * 1024;
     for (; i + 3 < n; i += stride) {
         float4 v = *reinterpret_cast<const float4 *>(x + i);
-        v.x = silu_ref(v.x); v.y = silu_ref(v.y); v.z = silu_ref(v.z); v.w = silu_ref(v.w);
+        v.x = ref_silu(v.x); v.y = ref_silu(v.y); v.z = ref_silu(v.z); v.w = ref_silu(v.w);
         *reinterpret_cast<float4 *>(y + i) = v;
     }
-    if (i < n) for (int64_t j = i; j < n && j < i + 4; ++j) y[j] = silu_ref(x[j]);
+    if (i < n) for (int64_t j = i; j < n && j < i + 4; ++j) y[j] = ref_silu(x[j]);
 }
 // CPUSiLU::execute calls mllm_vec_silu_f32 per (b, h, s) ROW (op/CPUSiLU.cpp:35-47): the dim % 8 trailing values of every row take the scalar mllm_silu_f32 = x / (1 + expf(-x)) with
 // libm's expf (ActivationFunction.cpp:24-26), the rest the polynomial.  Rows of a multiple of 8 (every model on the hot path) have no such tail: silu_kernel above.
@@ -391,7 +361,7 @@ __global__ __launch_bounds__(256) void silu_rows_kernel(const float *__restrict_
     const int full = dim & ~7;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * dim; i += (int64_t)gridDim.x * 256) {
         const float v = x[i];
-        y[i] = (int)(i % dim) < full ? silu_ref(v) : __fdiv_rn(v, __fadd_rn(1.0f, glibc_expf(-v, tab)));
+        y[i] = (int)(i % dim) < full ? ref_silu(v) : __fdiv_rn(v, __fadd_rn(1.0f, glibc_expf(-v, tab)));
     }
 }
 // silu(gate)*up of QWen2MLP (modeling_qwen2_vl.hpp:205-208) on a fused [M][2I] gate|up buffer
@@ -403,8 +373,8 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const float *__restrict__
         const float4 g = *reinterpret_cast<const float4 *>(gu + (int64_t)m * 2 * I + c);
         const float4 u = *reinterpret_cast<const float4 *>(gu + (int64_t)m * 2 * I + I + c);
         float4 o;
-        o.x = __fmul_rn(silu_ref(g.x), u.x); o.y = __fmul_rn(silu_ref(g.y), u.y);
-        o.z = __fmul_rn(silu_ref(g.z), u.z); o.w = __fmul_rn(silu_ref(g.w), u.w);
+        o.x = __fmul_rn(ref_silu(g.x), u.x); o.y = __fmul_rn(ref_silu(g.y), u.y);
+        o.z = __fmul_rn(ref_silu(g.z), u.z); o.w = __fmul_rn(ref_silu(g.w), u.w);
         *reinterpret_cast<float4 *>(y + e) = o;
     }
 }
@@ -429,7 +399,7 @@ __global__ __launch_bounds__(64 * QP_WAVES) void quantize_q8k_pack_act_kernel(co
             const int64_t K = (int64_t)nb * 256;
             const float4 g = reinterpret_cast<const float4 *>(x + (int64_t)m * 2 * K + i * 256)[lane];
             const float4 u = reinterpret_cast<const float4 *>(x + (int64_t)m * 2 * K + K + i * 256)[lane];
-            v = make_float4(__fmul_rn(silu_ref(g.x), u.x), __fmul_rn(silu_ref(g.y), u.y), __fmul_rn(silu_ref(g.z), u.z), __fmul_rn(silu_ref(g.w), u.w));
+            v = make_float4(__fmul_rn(ref_silu(g.x), u.x), __fmul_rn(ref_silu(g.y), u.y), __fmul_rn(ref_silu(g.z), u.z), __fmul_rn(ref_silu(g.w), u.w));
         }
     }
     wave_quant_pack(v, lane, live, pack, q4kp_tile_blocks(M, nb), nb, m, i);
@@ -454,7 +424,7 @@ __global__ __launch_bounds__(256) void binary_kernel(const float *__restrict__ a
 }
 
 // CPUSoftMax (op/CPUSoftMax.cpp:28-65 -> mllm_vec_soft_max_f32, ActivationFunction.cpp:29-80), one wave per row, every bit the reference's:
-// the columns go through in chunks of 8 -- y = v_expf(x - max) per lane, the chunk's sum in the AVX2 hsum order ((v4+v0)+(v6+v2)) + ((v5+v1)+(v7+v3)) -- and the
+// the columns go through in chunks of 8 -- y = ref_expf_poly(x - max) per lane, the chunk's sum in the AVX2 hsum order ((v4+v0)+(v6+v2)) + ((v5+v1)+(v7+v3)) -- and the
 // chunk sums are added to the row sum one after the other; the < 8 trailing columns use libm's expf (glibc_expf) and join the sum one by one; y *= 1 / sum.
 __global__ __launch_bounds__(64) void softmax_kernel(const float *__restrict__ x, float *__restrict__ y, int n, const int *__restrict__ valid) {
     __shared__ uint64_t tab[32];
@@ -472,7 +442,7 @@ __global__ __launch_bounds__(64) void softmax_kernel(const float *__restrict__ x
     for (int base = 0; base < nfull; base += 64) {      // eight chunks per pass, chunk g in lanes 8g .. 8g+7
         const int i = base + lane;
         float e = 0.0f;
-        if (i < nfull) { e = v_expf(__fsub_rn(xr[i], mx)); yr[i] = e; }
+        if (i < nfull) { e = ref_expf_poly(__fsub_rn(xr[i], mx)); yr[i] = e; }
         float t = __fadd_rn(e, __shfl_xor(e, 4));       // lanes 0..3 of the chunk: v[l+4] + v[l]
         t = __fadd_rn(t, __shfl_xor(t, 2));             // lane 0: t0 + t2, lane 1: t1 + t3
         t = __fadd_rn(t, __shfl_xor(t, 1));             // lane 0: (t0 + t2) + (t1 + t3)
@@ -492,7 +462,7 @@ __global__ __launch_bounds__(64) void softmax_kernel(const float *__restrict__ x
     for (int i = v + lane; i < n; i += 64) yr[i] = 0.0f;
 }
 
-// ---- the same softmax for ONE long row (a vocabulary: top-p sampling), spread over the chip.  What is order-free runs everywhere -- the maximum, y = v_expf(x - max) and
+// ---- the same softmax for ONE long row (a vocabulary: top-p sampling), spread over the chip.  What is order-free runs everywhere -- the maximum, y = ref_expf_poly(x - max) and
 // the sum of every 8-chunk in its hsum order --; the row sum is still the reference's: the chunk sums added one after the other, then the trailing columns.  One wave does
 // that with a travelling accumulator (lane l holds 16 consecutive chunk sums, a wave_ror hop between lanes: ln_fused_kernel's walk): 19 k dependent adds instead of the
 // 1.9 ms the single-wave kernel above spends on a 151,936-wide row.
@@ -515,7 +485,7 @@ __global__ __launch_bounds__(256) void softmax_row_exp_kernel(const float *__res
     const int nfull = n & ~7;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < ((n + 255) & ~255); i += gridDim.x * 256) {
         float e = 0.0f;
-        if (i < nfull) { e = v_expf(__fsub_rn(x[i], mx)); y[i] = e; }
+        if (i < nfull) { e = ref_expf_poly(__fsub_rn(x[i], mx)); y[i] = e; }
         else if (i < n) y[i] = glibc_expf(__fsub_rn(x[i], mx), tab);      // the < 8 trailing columns: libm's expf
         float t = __fadd_rn(e, __shfl_xor(e, 4));
         t = __fadd_rn(t, __shfl_xor(t, 2));
@@ -592,16 +562,11 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float *__restrict__ 
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < n; i += 1024) { const float v = x[i]; if (v > best) { best = v; bi = i; } }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(bi, m, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
+    wave_first_max(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+        fold_first_max<16>(sv, si, best, bi);
         *out = bi;
     }
 }
@@ -616,16 +581,11 @@ __device__ __forceinline__ void argmax_slice(const float *__restrict__ x, int n,
     float best = -INFINITY;
     int besti = 0x7fffffff;
     for (int i = lo + (int)threadIdx.x; i < hi; i += 256) { const float v = x[i]; if (v > best) { best = v; besti = i; } }      // a thread's indices ascend: strict > keeps the first
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(besti, m, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    wave_first_max(best, besti);
     if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) if (bv[w] > best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
+        fold_first_max<4>(bv, bi, best, besti);
         *slot_val = best;
         *slot_idx = besti;
     }
@@ -650,14 +610,9 @@ __global__ __launch_bounds__(1024) void seqs_next_kernel(SeqKV *__restrict__ seq
         for (int i = lane; i < nparts; i += 64) {
             const float v = part_val[(int64_t)w * nparts + i];
             const int ix = part_idx[(int64_t)w * nparts + i];
-            if (v > best || (v == best && ix < besti)) { best = v; besti = ix; }
+            first_max_merge(best, besti, v, ix);
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(best, m, 64);
-            const int oi = __shfl_xor(besti, m, 64);
-            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-        }
+        wave_first_max(best, besti);
         if (lane == 0) {
             int on = seqs[w].active;
             if (on) {
@@ -687,14 +642,9 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float *__restric
     for (int i = threadIdx.x; i < nparts; i += 64) {
         const float v = part_val[i];
         const int ix = part_idx[i];
-        if (v > best || (v == best && ix < besti)) { best = v; besti = ix; }
+        first_max_merge(best, besti, v, ix);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(besti, m, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    wave_first_max(best, besti);
     if (threadIdx.x == 0) *out = besti;
 }
 
@@ -736,7 +686,7 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float *__restrict__ x,
     }
 }
 
-// A8: dequantize_row_q4_0 (ggml QuantizeQ4.cpp:74-93) of row ids[s] from the nibble/scale planes: y = (nib-8)*d
+// A8: dequantize_row_q4_0 of row ids[s] from the nibble/scale planes (q40_value)
 __global__ __launch_bounds__(256) void embedding_q40_kernel(const float *__restrict__ ids, const uint8_t *__restrict__ Wqs, const uint16_t *__restrict__ Wd,
                                                             float *__restrict__ out, int hidden, int vocab) {
     const int s = blockIdx.x;
@@ -749,8 +699,8 @@ __global__ __launch_bounds__(256) void embedding_q40_kernel(const float *__restr
         const int blk = t >> 4, j = t & 15;
         const float d = h2f(dd[blk]);
         const uint8_t b = q[t];
-        o[blk * 32 + j] = __fmul_rn((float)((int)(b & 0xF) - 8), d);
-        o[blk * 32 + j + 16] = __fmul_rn((float)((int)(b >> 4) - 8), d);
+        o[blk * 32 + j] = q40_value(b & 0xF, d);
+        o[blk * 32 + j + 16] = q40_value(b >> 4, d);
     }
 }
 
@@ -764,8 +714,7 @@ __global__ __launch_bounds__(256) void repack_q40_kernel(const uint8_t *__restri
     }
 }
 
-// A10/A11/A19 rope_hf rotate (CPUMultimodalRoPE.cpp:153-221). The reference is built with GCC -O2 -mfma, whose default
-// contraction turns `a*c - b*s` into fma(a, c, -(b*s)) and `a*s + b*c` into fma(a, s, b*c).
+// A10/A11/A19 rope_hf rotate (rope_pair)
 template <bool OUT_F16>
 __global__ __launch_bounds__(256) void rope_apply_kernel(const float *__restrict__ x, int64_t ldx, const float *__restrict__ sin_t, const float *__restrict__ cos_t,
                                                          int ld_tab, void *__restrict__ out, int64_t ldo, int S, int H, int D, int period) {
@@ -779,8 +728,8 @@ __global__ __launch_bounds__(256) void rope_apply_kernel(const float *__restrict
         const int ts = period > 0 ? s % period : s;
         const float a = x[(int64_t)s * ldx + h * D + d], b = x[(int64_t)s * ldx + h * D + d + half];
         const float sv = sin_t[(int64_t)ts * ld_tab + d], cv = cos_t[(int64_t)ts * ld_tab + d];
-        const float v1 = __fmaf_rn(a, cv, -__fmul_rn(b, sv));
-        const float v2 = __fmaf_rn(a, sv, __fmul_rn(b, cv));
+        float v1, v2;
+        rope_pair(a, b, sv, cv, v1, v2);
         const int64_t o = (int64_t)s * ldo + h * D + d;
         if (OUT_F16) { reinterpret_cast<uint16_t *>(out)[o] = f2h(v1); reinterpret_cast<uint16_t *>(out)[o + half] = f2h(v2); }
         else { reinterpret_cast<float *>(out)[o] = v1; reinterpret_cast<float *>(out)[o + half] = v2; }
@@ -809,7 +758,8 @@ __global__ __launch_bounds__(256) void qkv_rope_append_kernel(float *__restrict_
             float *x = qkv + (int64_t)s_ * ldq + (isk ? Hq * D : 0) + h * D + d;
             const float a = x[0], b = x[half];
             const float sv = sin_t[(int64_t)s_ * ld_tab + d], cv = cos_t[(int64_t)s_ * ld_tab + d];
-            const float v1 = __fmaf_rn(a, cv, -__fmul_rn(b, sv)), v2 = __fmaf_rn(a, sv, __fmul_rn(b, cv));
+            float v1, v2;
+            rope_pair(a, b, sv, cv, v1, v2);
             if (isk) { uint16_t *o = kout + (int64_t)s_ * ldk + h * D + d; o[0] = f2h(v1); o[half] = f2h(v2); }
             else { x[0] = v1; x[half] = v2; }
         } else {
@@ -837,7 +787,8 @@ __global__ __launch_bounds__(256) void rope2_store2_kernel(const float *__restri
             const float *x = isk ? k : q;
             const float a = x[o], b = x[o + half];
             const float sv = isk ? sin_k[(int64_t)s_ * ld_tab_k + d] : sin_q[(int64_t)s_ * ld_tab_q + d], cv = isk ? cos_k[(int64_t)s_ * ld_tab_k + d] : cos_q[(int64_t)s_ * ld_tab_q + d];
-            const float v1 = __fmaf_rn(a, cv, -__fmul_rn(b, sv)), v2 = __fmaf_rn(a, sv, __fmul_rn(b, cv));
+            float v1, v2;
+            rope_pair(a, b, sv, cv, v1, v2);
             if (isk) { k_out[o] = v1; k_out[o + half] = v2; k16[o] = f2h(v1); k16[o + half] = f2h(v2); }
             else { q_out[o] = v1; q_out[o + half] = v2; }
         } else {
@@ -867,7 +818,8 @@ __global__ __launch_bounds__(256) void seqs_rope_append_kernel(float *__restrict
             float *x = row + (isk ? Hq * D : 0) + h * D + d;
             const float a = x[0], bb = x[half];
             const float sv = sin_t[tab + d], cv = cos_t[tab + d];
-            const float v1 = __fmaf_rn(a, cv, -__fmul_rn(bb, sv)), v2 = __fmaf_rn(a, sv, __fmul_rn(bb, cv));
+            float v1, v2;
+            rope_pair(a, bb, sv, cv, v1, v2);
             if (isk) { uint16_t *o = kout + h * D + d; o[0] = f2h(v1); o[half] = f2h(v2); }
             else { x[0] = v1; x[half] = v2; }
         } else {

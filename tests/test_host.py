@@ -56,6 +56,44 @@ def test_no_quantiser_in_the_tree():
                 assert "quantlib" not in src and "tests.fixtures" not in src, f
 
 
+def test_reference_rules_are_defined_once():
+    """Every arithmetic rule of the reference that several kernels need is written in mllm_amd/csrc/ref_arith.h and nowhere else under mllm_amd/csrc: the signature
+    text of each rule occurs in that header only, and the earlier per-file copies and inline spellings are gone."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "mllm_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip"))}
+    assert "ref_arith.h" in src
+    signatures = {
+        "mllm_v_expf polynomial": r"0x1\.715476p\+0f",
+        "Q8_0 rounding": r"\brintf\b",
+        "Q8_K / nearest_int magic add": r"12582912\.0f",
+        "first-maximum tie clause": r"v == best && i < besti",
+        "first-maximum tie clause, any names, as an unconditional merge": r"if \(\w+ > best \|\| \(\w+ == best && \w+ < \w+\)\)",
+        "Q4_0 nibble": r"\(nibble - 8\)",
+    }
+    for rule, pat in signatures.items():
+        where = [f for f, text in src.items() if re.search(pat, text)]
+        assert where == ["ref_arith.h"], (rule, where)
+    # rules whose spelling is too generic to search for: the header names them, and the old copies and inline spellings are gone
+    head = src["ref_arith.h"]
+    for name in ("ref_expf_poly", "ref_silu", "q80_scale", "q80_round4", "rope_pair", "first_max_merge", "wave_first_max", "rms_inv", "rms_scale", "q40_value",
+                 "q8k_first_max", "q8k_round4", "q8k_bytes", "q8k_sum4", "nearest_int"):
+        assert re.search(r"__forceinline__ [\w ]+\b%s\(" % name, head), name
+        assert not any(re.search(r"__forceinline__ [\w ]+\b%s\(" % name, text) for f, text in src.items() if f != "ref_arith.h"), name
+    gone = (r"v_expf_dec", r"silu_ref", r"\bv_expf\(", r"1\.0f \+ ref_expf_poly", r"__fadd_rn\(1\.0f, \w*expf_",      # SiLU re-spelled
+            r"__fmaf_rn\(\w+, \w+, -",                                                                       # the rotary pair's first product
+            r"sqrtf\(\(float\)\(ss|sqrtf\(m \+ eps\)|sqrtf\(__fadd_rn\(m,",                                 # RMSNorm after the sum of squares
+            r"\* inv\) \*|__fmul_rn\(__fmul_rn\(\S+ inv\)",
+            r"0xF\) - 8\)|>> 4\) - 8\)",                                                                      # the Q4_0 nibble
+            r"/ 127\.0f|127\.0f / |__fdiv_rn\(127\.0f",                                                       # Q8_0 scale
+            r"0x4B40007Fu")                                                                                  # Q8_K clamp on the bits
+    for pat in gone:
+        where = [f for f, text in src.items() if f != "ref_arith.h" and re.search(pat, text)]
+        assert not where, (pat, where)
+    assert "ref_arith.h" in open(os.path.join(root, "mllm_amd", "build.py")).read()
+
+
 def test_mllm_file_roundtrip(tmp_path):
     p = str(tmp_path / "t.mllm")
     a = np.arange(12, dtype=np.float32)
