@@ -19,7 +19,8 @@ def _stream():
 
 def _dev(x, dtype=None):
     if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
+        x = np.ascontiguousarray(x)
+        x = torch.from_numpy(x if x.flags.writeable else x.copy())      # (torch warns on read-only arrays; tests share theirs read-only)
     if dtype is not None:
         x = x.to(dtype)
     return x.contiguous().cuda()
@@ -58,16 +59,49 @@ def quantize_q80(x):
     return qs, d
 
 
-def linear_q4k(W_raw, x, N, bias=None, residual=None, out_f16=False, xq: Q8K | None = None):
-    """CPULinear with Q4_K weights: W_raw uint8 `[N * K/256 * 144]`, x fp32 `[M][K]`."""
+# Outputs with a pitch: a Linear entry given `ldy` writes rows of N values into rows of ldy.  The buffer is pre-filled with a bit pattern no kernel produces (a signalling
+# NaN with a payload), so the pad columns, and a whole output after a refused call, can be checked for stray stores.
+SENTINEL_F32, SENTINEL_F16, SENTINEL_BYTE = 0x7FA5A5A5, 0x7DA5, 0xA5
+GUARD_BYTES = 4096
+
+
+def sentinel_out(M, ld, f16=False):
+    """`[M][ld]` output (fp32 or fp16) holding the sentinel bit pattern in every element."""
+    if f16:
+        return torch.full((M, ld), SENTINEL_F16, dtype=torch.int16, device="cuda").view(torch.float16)
+    return torch.full((M, ld), SENTINEL_F32, dtype=torch.int32, device="cuda").view(torch.float32)
+
+
+def is_sentinel(t):
+    """Boolean array (host): which elements of `t` still hold the sentinel bit pattern."""
+    if t.dtype == torch.float16:
+        return t.view(torch.int16).cpu().numpy() == SENTINEL_F16
+    return t.view(torch.int32).cpu().numpy() == SENTINEL_F32
+
+
+def _out(M, N, ldy, f16, out):
+    """(output tensor, pitch): `out` as given, else `[M][N]` uninitialised when no pitch is asked for, else `[M][ldy]` filled with the sentinel."""
+    if out is not None:
+        assert out.shape[0] == M and out.dtype == (torch.float16 if f16 else torch.float32) and out.is_contiguous()
+        return out, out.shape[1]
+    if ldy is None:
+        return torch.empty((M, N), dtype=torch.float16 if f16 else torch.float32, device="cuda"), N
+    assert ldy >= N
+    return sentinel_out(M, ldy, f16), ldy
+
+
+def linear_q4k(W_raw, x, N, bias=None, residual=None, out_f16=False, xq: Q8K | None = None, ldy=None, out=None):
+    """CPULinear with Q4_K weights: W_raw uint8 `[N * K/256 * 144]`, x fp32 `[M][K]`.  With `ldy` the output is `[M][ldy]` (sentinel_out) and returned whole, and the
+    residual is `[M][ldy]` too; `out` is written in place of a fresh buffer (it stays readable when the call is refused)."""
     W = _dev(W_raw, torch.uint8)
     if xq is None:
         xq = quantize_q8k(x)
     M, K = xq.M, xq.K
     b = _dev(bias, torch.float32) if bias is not None else None
     r = _dev(residual, torch.float32) if residual is not None else None
-    y = torch.empty((M, N), dtype=torch.float16 if out_f16 else torch.float32, device="cuda")
-    check(L.load().mllm_hip_linear_q4k_q8k(vp(W), vp(b), vp(xq.qs), vp(xq.d), vp(xq.bsums), vp(y), C.c_int(F16 if out_f16 else F32), i64(N), vp(r),
+    y, ld = _out(M, N, ldy, out_f16, out)
+    assert r is None or tuple(r.shape) == (M, ld)
+    check(L.load().mllm_hip_linear_q4k_q8k(vp(W), vp(b), vp(xq.qs), vp(xq.d), vp(xq.bsums), vp(y), C.c_int(F16 if out_f16 else F32), i64(ld), vp(r),
                                            C.c_int(M), C.c_int(N), C.c_int(K), _stream()), "linear_q4k_q8k")
     return y
 
@@ -80,25 +114,66 @@ def repack_q40(raw, n_blocks):
     return qs, d
 
 
-def linear_q40(W_raw, x, N, bias=None):
+def linear_q40(W_raw, x, N, bias=None, ldy=None, out=None):
     x = _dev(x, torch.float32)
     M, K = x.shape
     Wqs, Wd = repack_q40(W_raw, N * K // 32)
     xqs, xd = quantize_q80(x)
     b = _dev(bias, torch.float32) if bias is not None else None
-    y = torch.empty((M, N), dtype=torch.float32, device="cuda")
-    check(L.load().mllm_hip_linear_q40_q80(vp(Wqs), vp(Wd), vp(b), vp(xqs), vp(xd), vp(y), i64(N), C.c_int(M), C.c_int(N), C.c_int(K), _stream()), "linear_q40_q80")
+    y, ld = _out(M, N, ldy, False, out)
+    check(L.load().mllm_hip_linear_q40_q80(vp(Wqs), vp(Wd), vp(b), vp(xqs), vp(xd), vp(y), i64(ld), C.c_int(M), C.c_int(N), C.c_int(K), _stream()), "linear_q40_q80")
     return y
 
 
-def linear_f32(W, x, bias=None):
+def _off16(t, off):
+    """`t` as it is (torch's allocations are 16-byte aligned), or the same values one float past a 16-byte boundary: a view one element into a larger buffer."""
+    if not off:
+        assert t.data_ptr() % 16 == 0
+        return t
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device="cuda")
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def linear_f32(W, x, bias=None, ldy=None, w_off=False, x_off=False):
+    """fp32 Linear.  `w_off` / `x_off` pass that operand 4 bytes past a 16-byte boundary (the matrix-core kernel needs both aligned: such a call takes the VALU kernel)."""
     W, x = _dev(W, torch.float32), _dev(x, torch.float32)
     M, K = x.shape
     N = W.numel() // K
+    W, x = _off16(W, w_off), _off16(x, x_off)
     b = _dev(bias, torch.float32) if bias is not None else None
-    y = torch.empty((M, N), dtype=torch.float32, device="cuda")
-    check(L.load().mllm_hip_linear_f32(vp(W), vp(b), vp(x), vp(y), i64(N), C.c_int(M), C.c_int(N), C.c_int(K), _stream()), "linear_f32")
+    y, ld = _out(M, N, ldy, False, None)
+    check(L.load().mllm_hip_linear_f32(vp(W), vp(b), vp(x), vp(y), i64(ld), C.c_int(M), C.c_int(N), C.c_int(K), _stream()), "linear_f32")
     return y
+
+
+def linear_workspace_bytes(wdtype, M, K):
+    return int(L.load().mllm_hip_linear_workspace_bytes(C.c_int(wdtype), C.c_int(M), C.c_int(K)))
+
+
+def linear(W, wdtype, x, N, bias=None, out_f16=False, ldy=None):
+    """mllm_hip_linear, the one-call CPULinear::execute: W = raw Q4_K blocks, raw Q4_0 blocks (re-ordered here into the layout the entry reads: the nibble plane, then the
+    fp16 scale plane at the 256-byte aligned offset N*K/2) or fp32 `[N][K]`; x fp32 `[M][K]`.  The workspace is exactly mllm_hip_linear_workspace_bytes long and is followed
+    by a guard band.  Returns (y `[M][ldy or N]`, pre-filled with the sentinel; whether the guard band is untouched)."""
+    x = _dev(x, torch.float32)
+    M, K = x.shape
+    if wdtype == Q4_0:
+        qs, d = repack_q40(W, N * K // 32)
+        doff = (N * K // 2 + 255) & ~255
+        Wd = torch.full((doff + 2 * d.numel(),), SENTINEL_BYTE, dtype=torch.uint8, device="cuda")
+        Wd[:qs.numel()] = qs
+        Wd[doff:] = d.view(torch.uint8)
+    else:
+        Wd = _dev(W, torch.float32 if wdtype == F32 else torch.uint8)
+    b = _dev(bias, torch.float32) if bias is not None else None
+    y, ld = _out(M, N, ldy if ldy is not None else N, out_f16, None)
+    wsb = linear_workspace_bytes(wdtype, M, K)
+    ws = torch.full((wsb + GUARD_BYTES,), SENTINEL_BYTE, dtype=torch.uint8, device="cuda")
+    check(L.load().mllm_hip_linear(vp(Wd), C.c_int(wdtype), vp(b), vp(x), vp(y), C.c_int(F16 if out_f16 else F32), i64(ld), C.c_int(M), C.c_int(N), C.c_int(K), vp(ws),
+                                   _stream()), "linear")
+    return y, bool((ws[wsb:] == SENTINEL_BYTE).all().item())
 
 
 def gemm_f32_bhsd(a, b):
