@@ -383,6 +383,25 @@ int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens,
  * side of the steps) may be NULL.  ERR_ARG: NULL model / first_tokens, no LLM, B < 1 or above batch_begin's, steps <= 0, a sequence without a prefill; ERR_SHAPE:
  * cache_len[b] + steps > cache_limit for some b (nothing changed).  After a failure inside the loop the host's counters are re-read from the device state. */
 int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out, float *elapsed_ms);
+/* Batched prefill: the prompts of sequences 0 .. B-1 of batch_begin in ONE pass over the weights, instead of B times batch_select + mllm_hip_model_prefill (the
+ * reference's hook: KVCache_batch, mllm/Types.hpp:26-33; the forward the demos run over the prompt, examples/demo_qwen2_vl.cpp:53-63, demo_qwen.cpp, demo_tinyllama.cpp).
+ * `ids` holds the B prompts concatenated, n_ids[b] the length of prompt b; sequence b's rows are appended to ITS cache behind the cache_len[b] tokens it already holds
+ * (a first prompt or a further turn).  The sum of n_ids rows runs through every row-wise Op once; the rotary + cache append and the causal attention run in
+ * variable-length forms that read a per-sequence descriptor from device memory, a sequence with fewer than four rows through the Br = Bc = 1 recurrence as in the
+ * ordinary call.  Sequence b's results -- its whole logit row, its greedy id, every K / V row it appended -- are, bit for bit, those of batch_select(b) +
+ * mllm_hip_model_prefill alone, and every sequence carries on by batch_decode, batch_generate, batch_select + decode / generate / generate_sampled, or a further
+ * ordinary or batched prefill.
+ * Images (QWEN2VL only): visual_dev (device fp32) holds the tower's output rows of the image prompts, one image after the other, as mllm_hip_model_vision writes them;
+ * image_meta is the one grid_thw all of them share; n_visual_rows[b] is 0 for a text prompt, else the rows of one image, and row i of sequence b's block goes to its i-th
+ * image_token_id position.  The tower is not run here.  All three may be NULL for text prompts.  LLaVA image prompts (the splice changes the length) stay with
+ * mllm_hip_model_prefill; LLaVA text prompts work.
+ * Outputs (each optional): logits_host `[B][vocab]` of every sequence's last row, next_tokens `[B]` (greedy argmax, first maximum), elapsed_ms (device time, inputs
+ * resident in HBM when it starts).
+ * ERR_ARG: NULL model / ids / n_ids, no LLM, B < 1 or above batch_begin's, some n_ids[b] <= 0, visual rows on a model without a Qwen2-VL tower or without visual_dev /
+ * image_meta.  ERR_SHAPE: cache_len[b] + n_ids[b] > cache_limit for some b; the sum of n_ids above cache_limit (the activation buffers hold cache_limit rows); a count
+ * of image tokens in prompt b that differs from n_visual_rows[b].  Nothing has changed after any of them, nor after a failure inside the pass. */
+int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int32_t *ids, const int32_t *n_ids, const float *visual_dev, const int32_t *image_meta,
+                                 const int32_t *n_visual_rows, float *logits_host /* [B][vocab] */, int32_t *next_tokens /* [B] */, float *elapsed_ms);
 /* `steps` greedy decode forwards back to back on the device (argmax on device, no per-token D2H): SURVEY N2, the loop of
  * Module::generate (mllm/Module.cpp:63-100) with the greedy method.  tokens_host receives the generated ids. */
 int mllm_hip_model_generate(mllm_hip_model *m, int32_t first_token, int steps, int32_t *tokens_host, float *elapsed_ms);

@@ -125,4 +125,34 @@ int seqs_fa2_decode_launch(const float *q, int64_t ldq, const SeqKV *seqs_dev, i
 int seqs_argmax_next_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, SeqKV *seqs_dev, BatchCtl *ctl, int *tok_out,
                             float *ids_f, int *history, int hist_ld, hipStream_t st);
 
+// ---- batched prefill (engine.hip: mllm_hip_model_batch_prefill): the prompts of B sequences sit concatenated, sequence after sequence, in the activation buffers ----
+// One sequence's share of the pass.  The host knows every length, fills the array and uploads it once per call; the kernels read it from device memory.
+struct PrefillSeq {
+    uint16_t *k; uint16_t *v;   // the sequence's KV slabs (bases of layer 0)
+    int row0;                   // its first row in the concatenated buffers (and in the concatenated rotary table)
+    int S;                      // its prompt rows
+    int T0;                     // tokens its cache holds before the call
+    int Sk;                     // T0 + S: the keys its last row sees
+    int sk_eff;                 // the key columns the reference's tiling walks (launch_fa2: Tc = Sk / 4, Tc * 4 + (Tc ? Sk % Tc : 0) for fp16 K / V)
+    int pad;
+};
+// one query row of a sequence with fewer than four prompt rows: the reference's Br = Bc = 1 recurrence, the decode walk of row `row` over keys 0 .. t
+struct PrefillRow { uint16_t *k; uint16_t *v; int t; int row; };
+// rows [row0, row0 + S) of qkv: q rotated in place, k rotated -> fp16 rows T0 .. T0 + S - 1 of the sequence's K slab, v -> columns T0 .. of its transposed V slab
+// (qkv_rope_append_kernel's arithmetic); row r takes row r of the concatenated table.  One launch for all B sequences; max_S = the longest S (sizes the grid).
+// The host has checked T0 + S <= the slabs' capacity for every sequence.
+int prefill_seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, const PrefillSeq *seqs_dev, int64_t layer_k_off,
+                                    int64_t layer_v_off, int64_t ldk, int64_t ldvt, int B, int max_S, int Hq, int Hkv, int D, hipStream_t st);
+// causal __fa2_prefill_append (Br = Bc = 4) of every sequence with S >= 4 in one launch: fa2_prefill_kernel<D, true, true>'s body, blockIdx.z = sequence, its rows, slabs
+// and key counts read from its descriptor; a sequence with S < 4 is left to prefill_rows_fa2_decode_launch.  D = 64 or 128.
+int prefill_seqs_fa2_launch(const float *q, int64_t ldq, const PrefillSeq *seqs_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o, int64_t ldo,
+                            int B, int max_S, int Hq, int Hkv, int D, hipStream_t st);
+// __fa2_decode of n_rows single query rows, each over its own sequence's keys 0 .. t (fa2_decode_seqs_kernel's body, the row's place in q / o read from its descriptor)
+int prefill_rows_fa2_decode_launch(const float *q, int64_t ldq, const PrefillRow *rows_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o,
+                                   int64_t ldo, int n_rows, int Hq, int Hkv, int D, int cap, hipStream_t st);
+// dst[b][:] = src[rows[b]][:] for b < B (the last row of every sequence, gathered for the head); dim a multiple of 4
+int gather_rows_launch(const float *src, const int *rows_dev, float *dst, int B, int dim, hipStream_t st);
+// B first-maximum argmaxes (std::max_element per row) -> tok_out[b]; part_val / part_idx hold B * nparts entries
+int rows_argmax_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, int *tok_out, hipStream_t st);
+
 }  // namespace mllm_hip

@@ -234,6 +234,8 @@ struct mllm_hip_model {
     int cur_seq = 0;
     int gemm_min_rows = 16;      // rows from which a Linear takes the packed MFMA GEMM (its 32-row tile costs the same for 1 .. 32 rows); a batched step of B >= 4 lowers it to B
     SeqKV *seqkv_dev = nullptr;
+    uint8_t *pf_pin = nullptr; size_t pf_pin_bytes = 0;      // batch_prefill / batch_decode: page-locked staging of what a call uploads and reads back (ensure_batch_pin)
+    PrefillSeq *pf_seqs = nullptr; PrefillRow *pf_rows = nullptr; int *pf_last = nullptr;      // batched prefill: descriptors of batch_cap sequences, of their (at most 3 each) Br = 1 rows, their last rows
     bool needs_arm = false;      // a batched step moved the selected sequence on: the fused decode step's device state is re-armed before its next use
     float *blogits = nullptr, *bnormed = nullptr; int8_t *bx80_qs = nullptr; uint16_t *bx80_d = nullptr; int *btok = nullptr; int batch_cap = 0;
     // the batched step's device state beside the SeqKV descriptors: the rotary table [cache_limit][D/2] (built on first batched use), the batch's control words, the ids
@@ -604,6 +606,7 @@ extern "C" void mllm_hip_model_destroy(mllm_hip_model *m) {
     for (int b = 0; b < 2; ++b) { if (m->vup[b]) (void)hipEventDestroy(m->vup[b]); if (m->vfree[b]) (void)hipEventDestroy(m->vfree[b]); }
     if (m->pin_tok) (void)hipHostFree(m->pin_tok);
     if (m->pin_err) (void)hipHostFree(m->pin_err);
+    if (m->pf_pin) (void)hipHostFree(m->pf_pin);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     if (m->mrope_host_free) (void)hipEventDestroy(m->mrope_host_free);
@@ -1220,6 +1223,7 @@ extern "C" int mllm_hip_model_batch_begin(mllm_hip_model *m, int B) {
         EH(m->dalloc(&m->blogits, (size_t)B * c.vocab * 4)); EH(m->dalloc(&m->bnormed, (size_t)B * c.hidden * 4));
         EH(m->dalloc(&m->bx80_qs, (size_t)B * c.hidden)); EH(m->dalloc(&m->bx80_d, (size_t)B * (c.hidden / 32) * 2 + 64)); EH(m->dalloc(&m->btok, (size_t)B * 4));
         EH(m->dalloc(&m->seqkv_dev, (size_t)B * sizeof(SeqKV)));
+        EH(m->dalloc(&m->pf_seqs, (size_t)B * sizeof(PrefillSeq))); EH(m->dalloc(&m->pf_rows, (size_t)3 * B * sizeof(PrefillRow))); EH(m->dalloc(&m->pf_last, (size_t)B * 4));
         EH(m->dalloc(&m->bhist, (size_t)B * c.cache_limit * 4));
         m->batch_cap = B;
     }
@@ -1316,6 +1320,16 @@ static int batch_step_body(M *m, int B) {
     const int np = std::max(1, std::min(m->max_parts / B, 128));
     return seqs_argmax_next_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
 }
+// the batched entry points' page-locked staging block (grown on demand; nothing of it is in flight between calls: every call ends with a synchronisation)
+static int ensure_batch_pin(M *m, size_t need_b) {
+    if (need_b > m->pf_pin_bytes) {
+        if (m->pf_pin) HH(hipHostFree(m->pf_pin));
+        m->pf_pin = nullptr; m->pf_pin_bytes = 0;
+        HH(hipHostMalloc((void **)&m->pf_pin, need_b, hipHostMallocDefault));
+        m->pf_pin_bytes = need_b;
+    }
+    return 0;
+}
 extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
     if (!m || !m->has_llm || !tokens || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
     EH(batch_check(m, B, 1, "mllm_hip_model_batch_decode"));
@@ -1326,9 +1340,15 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
     EH(batch_step_body(m, B));
     m->beager |= 1u << B;
     HH(hipEventRecord(m->ev1, st));
-    if (logits_host) HH(hipMemcpyAsync(logits_host, m->blogits, (size_t)B * c.vocab * 4, hipMemcpyDeviceToHost, st));
-    if (next_tokens) HH(hipMemcpyAsync(next_tokens, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    // the B logit rows come back through the page-locked block (a row set of some size read straight into the caller's pageable buffer leaves the runtime's on-the-fly
+    // page-lock of that range behind; see mllm_hip_model_batch_prefill)
+    const size_t lg_bytes = logits_host ? (size_t)B * c.vocab * 4 : 0;
+    EH(ensure_batch_pin(m, lg_bytes + (size_t)B * 4));
+    if (logits_host) HH(hipMemcpyAsync(m->pf_pin, m->blogits, lg_bytes, hipMemcpyDeviceToHost, st));
+    if (next_tokens) HH(hipMemcpyAsync(m->pf_pin + lg_bytes, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HH(hipStreamSynchronize(st));
+    if (logits_host) memcpy(logits_host, m->pf_pin, lg_bytes);
+    if (next_tokens) memcpy(next_tokens, m->pf_pin + lg_bytes, (size_t)B * 4);
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
     for (int b = 0; b < B; ++b) { m->seqs[b].cache_len += 1; m->seqs[b].last_pos += 1.0f; }
     if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
@@ -1402,6 +1422,176 @@ extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int
         HH(hipMemcpy2D(tokens_host, (size_t)steps * 4, m->bhist, (size_t)m->c.cache_limit * 4, (size_t)steps * 4, B, hipMemcpyDeviceToHost));
         for (int b = 0; b < B; ++b) for (int s = desc[b].made; s < steps; ++s) tokens_host[(size_t)b * steps + s] = -1;
     }
+    return MLLM_HIP_OK;
+}
+
+// ---- batched prefill: the prompts of sequences 0 .. B-1 in ONE pass over the weights ---------------------------------------------------------------------------------
+// The R = sum of S_b prompt rows sit concatenated, sequence after sequence, in the activation buffers and run through forward_llm's per-layer Ops once: everything
+// row-wise (norms, quantisers, Linears -- the packed GEMM from 16 rows, the GEMV below, as lin() chooses -- SiLU, residual adds) over all R rows, the two Ops that see a
+// sequence -- rotary + cache append, causal attention -- in their variable-length forms, which read a per-sequence descriptor from device memory (decode_launch.h
+// PrefillSeq).  A sequence with fewer than four rows takes the reference's Br = Bc = 1 recurrence, as launch_fa2 does for Sq < 4: its rows go through the decode walk
+// (PrefillRow), never through the 32-row kernel.  The head runs over the B last rows, gathered, with the B-row calls of batch_step_body.  Sequence b's results are, bit
+// for bit, those of batch_select(b) + mllm_hip_model_prefill alone (tests/test_batch_prefill.py).
+namespace {
+struct PrefillPlan {
+    int R = 0, max_S = 0, n_short = 0, n_vis = 0;
+    std::vector<PrefillSeq> desc;
+    std::vector<PrefillRow> rows;
+    std::vector<int> last, where;
+    std::vector<float> last_pos;
+};
+}  // namespace
+// embeddings of the R rows in m->h0, rotary tables in m->rope_sin / rope_cos, descriptors uploaded -> logits of every sequence's last row in m->blogits, ids in m->btok
+static int forward_llm_batch(M *m, int B, const PrefillPlan &pp) {
+    const auto &c = m->c;
+    const int H = c.hidden, I = c.inter, D = m->D, half = D / 2, R = pp.R;
+    hipStream_t st = m->st;
+    float *h = m->h0, *h2 = m->h1;
+    for (int li = 0; li < c.layers; ++li) {
+        auto &L = m->layers[li];
+        const int64_t koff = (int64_t)li * c.cache_limit * m->KVD, voff = (int64_t)li * m->KVD * m->vt_ld;
+        EH(q_rmsnorm(m, h, L.in_norm, m->xq, R, H, c.rms_eps));
+        EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, R));
+        EH(prefill_seqs_rope_append_launch(m->qkv, m->QKV, m->rope_sin, m->rope_cos, half, m->pf_seqs, koff, voff, m->KVD, m->vt_ld, B, pp.max_S, c.heads, c.kv_heads, D, st));
+        EH(prefill_seqs_fa2_launch(m->qkv, m->QKV, m->pf_seqs, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, B, pp.max_S, c.heads, c.kv_heads, D, st));
+        EH(prefill_rows_fa2_decode_launch(m->qkv, m->QKV, m->pf_rows, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, pp.n_short, c.heads, c.kv_heads, D, c.cache_limit, st));
+        EH(q_quant(m, m->attn, m->xq, R, m->HD));
+        EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, R));
+        EH(q_rmsnorm(m, h2, L.post_norm, m->xq, R, H, c.rms_eps));
+        EH(lin(m, L.gu, m->xq, m->gu, MLLM_HIP_F32, 2 * I, nullptr, R));
+        EH(q_silu_mul_quant(m, m->gu, m->act, m->xq2, R, I));
+        EH(lin(m, L.down, m->xq2, h, MLLM_HIP_F32, H, h2, R));
+    }
+    // the last row of every sequence, gathered into B contiguous rows (h2 is free after the last layer), then the final norm and the head over the B rows
+    EH(gather_rows_launch(h, m->pf_last, h2, B, H, st));
+    if (c.tie_embedding) {
+        EH(mllm_hip_rmsnorm(h2, m->final_norm, m->bnormed, nullptr, nullptr, nullptr, B, H, c.final_eps, 0, st));
+        EH(mllm_hip_quantize_q80(m->bnormed, m->bx80_qs, m->bx80_d, B, H, st));
+        EH(mllm_hip_linear_q40_q80(m->emb_qs, m->emb_d, nullptr, m->bx80_qs, m->bx80_d, m->blogits, c.vocab, B, c.vocab, H, st));
+    } else {
+        EH(mllm_hip_rmsnorm(h2, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, B, H, c.final_eps, 0, st));
+        EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->blogits, MLLM_HIP_F32, c.vocab, nullptr, B, c.vocab, H, st));
+    }
+    const int np = std::max(1, std::min(m->max_parts / B, 128));
+    return rows_argmax_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->btok, st);
+}
+extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int32_t *ids, const int32_t *n_ids, const float *visual_dev, const int32_t *image_meta,
+                                            const int32_t *n_visual_rows, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
+    if (!m || !m->has_llm || !ids || !n_ids || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
+    const auto &c = m->c;
+    seq_park(m);
+    bool has_vis = false;
+    for (int b = 0; b < B; ++b) {
+        if (n_ids[b] <= 0) { set_error_msg("mllm_hip_model_batch_prefill: sequence %d has an empty prompt", b); return MLLM_HIP_ERR_ARG; }
+        if (n_visual_rows && n_visual_rows[b] < 0) return MLLM_HIP_ERR_ARG;
+        if (n_visual_rows && n_visual_rows[b] > 0) has_vis = true;
+    }
+    int vrows = 0;
+    if (has_vis) {
+        // (a LLaVA image splice changes the sequence length: those prompts stay with mllm_hip_model_prefill)
+        if (m->vkind != V_QWEN2VL) { set_error_msg("mllm_hip_model_batch_prefill: visual rows need a model with a Qwen2-VL tower"); return MLLM_HIP_ERR_ARG; }
+        if (!visual_dev || !image_meta) return MLLM_HIP_ERR_ARG;
+        int nt, vcols; size_t ie;
+        vision_dims(m, image_meta, &nt, &vrows, &vcols, &ie);
+    }
+    PrefillPlan pp;
+    pp.desc.resize(B); pp.last.resize(B); pp.last_pos.resize(B);
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const int S = n_ids[b], T0 = m->seqs[b].cache_len;
+        if ((int64_t)T0 + S > c.cache_limit) { set_error_msg("mllm_hip_model_batch_prefill: KV cache overflow of sequence %d (%d + %d > %d)", b, T0, S, c.cache_limit); return MLLM_HIP_ERR_SHAPE; }
+        total += S;
+    }
+    if (total > c.cache_limit) {
+        set_error_msg("mllm_hip_model_batch_prefill: %lld prompt rows in one pass, the activation buffers hold cache_limit = %d rows", (long long)total, c.cache_limit);
+        return MLLM_HIP_ERR_SHAPE;
+    }
+    const int R = (int)total, half = m->D / 2;
+    for (int b = 0, row0 = 0; b < B; row0 += n_ids[b], ++b) {
+        const int S = n_ids[b], T0 = m->seqs[b].cache_len, Sk = T0 + S, Tc = Sk / 4;
+        pp.desc[b] = PrefillSeq{m->seqs[b].kslab, m->seqs[b].vslab, row0, S, T0, Sk, Tc * 4 + (Tc ? Sk % Tc : 0), 0};      // sk_eff: launch_fa2's expression for fp16 K / V
+        pp.last[b] = row0 + S - 1;
+        pp.max_S = std::max(pp.max_S, S);
+        if (S < 4) for (int r = 0; r < S; ++r) pp.rows.push_back(PrefillRow{m->seqs[b].kslab, m->seqs[b].vslab, T0 + r, row0 + r});
+        if (has_vis || m->vkind == V_QWEN2VL) {      // a model with the tower: every image token of a prompt stands for one visual row
+            const int want = has_vis ? n_visual_rows[b] : 0;
+            int have = 0;
+            for (int j = 0; j < S; ++j) if (ids[row0 + j] == c.image_token_id) { pp.where.push_back(row0 + j); ++have; }
+            if (have != want || (want != 0 && want != vrows)) {
+                set_error_msg("mllm_hip_model_batch_prefill: sequence %d has %d image tokens and %d visual rows (an image of this grid gives %d)", b, have, want, vrows);
+                return MLLM_HIP_ERR_SHAPE;
+            }
+        }
+    }
+    pp.R = R; pp.n_short = (int)pp.rows.size(); pp.n_vis = (int)pp.where.size();
+    // rotary rows of the R positions.  HF rotary: row r of sequence b is position T0_b + r (CPURoPE's h_cnt_); M-RoPE: get_rope_index per sequence on its own ids, the
+    // position ids concatenated along the sequence axis and handed to the one table builder
+    // Everything the call uploads, and what it reads back, is staged in ONE page-locked block of the engine's own (pin_tok's rule: no pageable staging).  An asynchronous
+    // copy on pageable memory makes the runtime page-lock the caller's range on the fly and keep that mapping; the engine does not leave such mappings of memory it does
+    // not own behind.
+    const size_t n_tab = (size_t)R * half;
+    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t o_sin = 0, o_cos = o_sin + up64(n_tab * 4), o_ids = o_cos + up64(n_tab * 4), o_desc = o_ids + up64((size_t)R * 4), o_last = o_desc + up64((size_t)B * sizeof(PrefillSeq)),
+                 o_rows = o_last + up64((size_t)B * 4), o_where = o_rows + up64((size_t)pp.n_short * sizeof(PrefillRow)), o_tok = o_where + up64((size_t)pp.n_vis * 4),
+                 o_logits = o_tok + up64((size_t)B * 4), need_b = o_logits + (logits_host ? (size_t)B * c.vocab * 4 : 0);
+    EH(ensure_batch_pin(m, need_b));
+    float *ts = reinterpret_cast<float *>(m->pf_pin + o_sin), *tc = reinterpret_cast<float *>(m->pf_pin + o_cos), *idf = reinterpret_cast<float *>(m->pf_pin + o_ids);
+    // rotary rows of the R positions.  HF rotary: row r of sequence b is position T0_b + r (CPURoPE's h_cnt_); M-RoPE: get_rope_index per sequence on its own ids, the
+    // position ids concatenated along the sequence axis and handed to the one table builder
+    if (m->mrope) {
+        std::vector<float> pos3((size_t)3 * R), pos;
+        for (int b = 0; b < B; ++b) {
+            const int S = n_ids[b], row0 = pp.desc[b].row0;
+            rope_index(m, ids + row0, S, image_meta, has_vis && n_visual_rows[b] > 0, pos);
+            for (int a = 0; a < 3; ++a) memcpy(&pos3[(size_t)a * R + row0], &pos[(size_t)a * S], (size_t)S * 4);
+            pp.last_pos[b] = pos[(size_t)S - 1];
+        }
+        EH(mllm_hip_mrope_table(c.rope_theta, m->D, pos3.data(), R, c.mrope_section, 3, ts, tc));
+    } else {
+        for (int b = 0; b < B; ++b) {
+            const size_t n = (size_t)n_ids[b] * half, src = (size_t)pp.desc[b].T0 * half, dst = (size_t)pp.desc[b].row0 * half;
+            memcpy(ts + dst, &m->hf_sin[src], n * 4); memcpy(tc + dst, &m->hf_cos[src], n * 4);
+            pp.last_pos[b] = (float)(pp.desc[b].Sk - 1);
+        }
+    }
+    for (int i = 0; i < R; ++i) idf[i] = (float)ids[i];
+    memcpy(m->pf_pin + o_desc, pp.desc.data(), (size_t)B * sizeof(PrefillSeq));
+    memcpy(m->pf_pin + o_last, pp.last.data(), (size_t)B * 4);
+    if (pp.n_short) memcpy(m->pf_pin + o_rows, pp.rows.data(), (size_t)pp.n_short * sizeof(PrefillRow));
+    if (pp.n_vis) memcpy(m->pf_pin + o_where, pp.where.data(), (size_t)pp.n_vis * 4);
+    hipStream_t st = m->st;
+    HH(hipMemcpyAsync(m->rope_sin, ts, n_tab * 4, hipMemcpyHostToDevice, st));
+    HH(hipMemcpyAsync(m->rope_cos, tc, n_tab * 4, hipMemcpyHostToDevice, st));
+    HH(hipMemcpyAsync(m->ids_f, idf, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    HH(hipMemcpyAsync(m->pf_seqs, m->pf_pin + o_desc, (size_t)B * sizeof(PrefillSeq), hipMemcpyHostToDevice, st));
+    HH(hipMemcpyAsync(m->pf_last, m->pf_pin + o_last, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (pp.n_short) HH(hipMemcpyAsync(m->pf_rows, m->pf_pin + o_rows, (size_t)pp.n_short * sizeof(PrefillRow), hipMemcpyHostToDevice, st));
+    if (pp.n_vis) HH(hipMemcpyAsync(m->idx_i, m->pf_pin + o_where, (size_t)pp.n_vis * 4, hipMemcpyHostToDevice, st));
+    HH(hipStreamSynchronize(st));      // the inputs are resident when the clock starts
+    HH(hipEventRecord(m->ev0, st));
+    EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, R, c.hidden, c.vocab, st));
+    // row i of the image prompts' tower output goes to the i-th image token of the concatenated prompts (where + index_put, modeling_qwen2_vl.hpp:386-393)
+    if (pp.n_vis) EH(mllm_hip_index_put_rows(m->h0, visual_dev, m->idx_i, pp.n_vis, c.hidden, st));
+    EH(forward_llm_batch(m, B, pp));
+    HH(hipEventRecord(m->ev1, st));
+    if (logits_host) HH(hipMemcpyAsync(m->pf_pin + o_logits, m->blogits, (size_t)B * c.vocab * 4, hipMemcpyDeviceToHost, st));
+    if (next_tokens) HH(hipMemcpyAsync(m->pf_pin + o_tok, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    // a decode step before this call may have left the merged launches' time-out flag set: it is reported (and cleared) here as finish() does, not handed on
+    if (m->plan.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, st));
+    HH(hipStreamSynchronize(st));
+    if (m->plan.merge_o && *m->pin_err) {
+        *m->pin_err = 0;
+        HH(hipMemset(m->poll_err, 0, 4));
+        set_error_msg("mllm_hip_model_batch_prefill: a merged decode launch before this call timed out waiting for its producer workgroups (option merge_o)");
+        return MLLM_HIP_ERR_ARG;
+    }
+    if (logits_host) memcpy(logits_host, m->pf_pin + o_logits, (size_t)B * c.vocab * 4);
+    if (next_tokens) memcpy(next_tokens, m->pf_pin + o_tok, (size_t)B * 4);
+    if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
+    // the host's counters move only now, when the whole pass has run: after a failure above they still describe the caches as they were (the rows a failed pass
+    // appended lie beyond every cache_len)
+    for (int b = 0; b < B; ++b) { m->seqs[b].cache_len = pp.desc[b].Sk; m->seqs[b].last_pos = pp.last_pos[b]; }
+    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
     return MLLM_HIP_OK;
 }
 

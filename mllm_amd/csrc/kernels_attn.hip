@@ -51,15 +51,30 @@ __device__ unsigned long long g_fa_stamps[64];
 typedef float v16f_t __attribute__((ext_vector_type(16)));
 
 // (head sizes up to 80 fit 168 registers and 44 KiB of LDS: three workgroups per CU, whose barrier / softmax / fetch phases run under each other's MFMAs)
-template <int D, bool F16, bool VT = false>
+// SEQS (batched prefill, causal, fp16 K rows + transposed fp16 V slab): the prompt rows of B sequences sit concatenated in Q / O and blockIdx.z = sequence; its first
+// row, row count, key counts and slabs come from its descriptor in device memory (uniform loads: the body keeps its registers) instead of the kernel arguments, of which
+// Sq / Sk / sk_eff / K / V / bq / bo are then unused and bk / bv are the layer's element offsets into every sequence's slabs.  A compile-time switch: the other
+// instantiations are the code they were.
+template <int D, bool F16, bool VT = false, bool SEQS = false>
 __global__ __launch_bounds__(256, (D <= 80 ? 3 : 2)) void fa2_prefill_kernel(const float *__restrict__ Q, int64_t ldq, const void *__restrict__ K, int64_t ldk,
                                                           const void *__restrict__ V, int64_t ldv, float *__restrict__ O, int64_t ldo, int Sq, int Sk,
-                                                          int sk_eff, int Hq, int Hkv, int causal, int64_t bq, int64_t bk, int64_t bv, int64_t bo) {
+                                                          int sk_eff, int Hq, int Hkv, int causal, int64_t bq, int64_t bk, int64_t bv, int64_t bo,
+                                                          const PrefillSeq *__restrict__ seqs) {
+    if constexpr (SEQS) {
+        static_assert(F16 && VT, "the engine's KV slabs");
+        const PrefillSeq sq = seqs[blockIdx.z];
+        Q += (int64_t)sq.row0 * ldq;
+        O += (int64_t)sq.row0 * ldo;
+        K = sq.k + bk;
+        V = sq.v + bv;
+        Sq = sq.S; Sk = sq.Sk; sk_eff = sq.sk_eff;
+    } else {
     // blockIdx.z = which of the independent (q, k, v, o) sets of the launch (the images of a vision pass); strides in elements
     Q += (int64_t)blockIdx.z * bq;
     O += (int64_t)blockIdx.z * bo;
     K = reinterpret_cast<const char *>(K) + (int64_t)blockIdx.z * bk * (F16 ? 2 : 4);
     V = reinterpret_cast<const char *>(V) + (int64_t)blockIdx.z * bv * (F16 ? 2 : 4);
+    }
     static_assert(D % 16 == 0 && D <= 128, "head dim");
     constexpr int NS = D / 16;              // MFMAs per score chain
     constexpr int KP = D + 4;               // K row pitch in LDS: a multiple of four floats, so a staged group is ONE 16-byte store (with the odd pitch D + 1 it was four
@@ -82,6 +97,9 @@ __global__ __launch_bounds__(256, (D <= 80 ? 3 : 2)) void fa2_prefill_kernel(con
     if ((Hq & 7) == 0) { const int lin = blockIdx.x + gridDim.x * blockIdx.y; head = lin % Hq; rb = lin / Hq; }
     const int kvh = head / (Hq / Hkv);
     const int r0 = rb * FA_R;
+    // the grid covers the longest sequence: a workgroup whose row block lies beyond its own sequence's rows leaves here, before the first barrier and LDS write; so does
+    // every workgroup of a sequence with fewer than four rows, which takes the Br = Bc = 1 recurrence (fa2_decode_rows_kernel) instead
+    if constexpr (SEQS) { if (Sq < 4 || r0 >= Sq) return; }
     const int delta = Sk - Sq;
     const float scale = 1.0f / sqrtf((float)D);
     // this lane's query operands: row r0 + col, dims 8(2s+h) + l for the wave's two chains
@@ -443,6 +461,63 @@ int seqs_fa2_decode_launch(const float *q, int64_t ldq, const SeqKV *seqs_dev, i
     default: return MLLM_HIP_ERR_SHAPE;
     }
 }
+// single query rows of sequences with fewer than four prompt rows (batched prefill): blockIdx.y = row descriptor {slabs, t, row}; fa2_decode_seqs_kernel's body
+template <int D, int NT>
+__global__ __launch_bounds__(NT) void fa2_decode_rows_kernel(const float *__restrict__ Q, int64_t ldq, const PrefillRow *__restrict__ rows, int64_t layer_k_off, int64_t layer_v_off,
+                                                             int64_t ldk, int64_t ldv, float *__restrict__ O, int64_t ldo, int cap, int nslots, int Hq, int Hkv) {
+    extern __shared__ __attribute__((aligned(16))) char fa_smem[];
+    const int head = blockIdx.x, kvh = head / (Hq / Hkv);
+    const PrefillRow rw = rows[blockIdx.y];
+    const void *K = rw.k + layer_k_off, *V = rw.v + layer_v_off;
+    DecodePrefetch<D, true, NT, true> P;
+    fa2_decode_prefetch<D, true, NT, true>(P, K, ldk, V, ldv, kvh * D, cap, nslots);
+    const int Sk = min(rw.t + 1, cap);
+    const DecodeLds L = carve_decode(fa_smem, cap, D, NT, nslots);
+    if (threadIdx.x < D) L.qs[threadIdx.x] = Q[(int64_t)rw.row * ldq + head * D + threadIdx.x];
+    __syncthreads();
+    fa2_decode_head<D, true, NT, true>(L, P, K, ldk, V, ldv, kvh * D, kvh * D, Sk, cap, nullptr, nullptr, -1);
+    if (threadIdx.x < D) O[(int64_t)rw.row * ldo + head * D + threadIdx.x] = L.ob[threadIdx.x];
+}
+template <int D>
+static int launch_fa2_rows(const float *q, int64_t ldq, const PrefillRow *rows_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o, int64_t ldo,
+                           int n_rows, int Hq, int Hkv, int cap, hipStream_t st) {
+    constexpr int NT = 1024;
+    const int nslots = decode_lds_slots(cap, D, NT, 2, true);
+    const size_t lds = decode_lds_bytes(cap, D, NT, 2, nslots, true);
+    if (lds > 160 * 1024) return MLLM_HIP_ERR_SHAPE;
+    auto kern = fa2_decode_rows_kernel<D, NT>;
+    if (lds > 48 * 1024) MH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(Hq, n_rows), dim3(NT), lds, st, q, ldq, rows_dev, layer_k_off, layer_v_off, ldk, ldvt, o, ldo, cap, nslots, Hq, Hkv);
+    return MH_LAUNCH_OK("fa2_decode_rows");
+}
+int prefill_rows_fa2_decode_launch(const float *q, int64_t ldq, const PrefillRow *rows_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o,
+                                   int64_t ldo, int n_rows, int Hq, int Hkv, int D, int cap, hipStream_t st) {
+    if (n_rows <= 0) return MLLM_HIP_OK;
+    if (!q || !o || !rows_dev || Hq <= 0 || Hkv <= 0 || Hq % Hkv || (ldk % 8) || (ldvt % 8) || n_rows > 65535) return MLLM_HIP_ERR_ARG;
+    switch (D) {
+    case 64: return launch_fa2_rows<64>(q, ldq, rows_dev, layer_k_off, layer_v_off, ldk, ldvt, o, ldo, n_rows, Hq, Hkv, cap, st);
+    case 128: return launch_fa2_rows<128>(q, ldq, rows_dev, layer_k_off, layer_v_off, ldk, ldvt, o, ldo, n_rows, Hq, Hkv, cap, st);
+    default: return MLLM_HIP_ERR_SHAPE;
+    }
+}
+int prefill_seqs_fa2_launch(const float *q, int64_t ldq, const PrefillSeq *seqs_dev, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk, int64_t ldvt, float *o, int64_t ldo,
+                            int B, int max_S, int Hq, int Hkv, int D, hipStream_t st) {
+    if (B <= 0 || max_S < 4) return MLLM_HIP_OK;      // (no sequence takes the Br = Bc = 4 form)
+    if (!q || !o || !seqs_dev || Hq <= 0 || Hkv <= 0 || Hq % Hkv || (ldk % 8) || (ldvt % 8) || B > 65535) return MLLM_HIP_ERR_ARG;
+    const dim3 grid((max_S + FA_R - 1) / FA_R, Hq, B);
+    switch (D) {
+#define FA2_SEQS(DD)                                                                                                                                                  \
+    case DD:                                                                                                                                                          \
+        hipLaunchKernelGGL((fa2_prefill_kernel<DD, true, true, true>), grid, dim3(256), 0, st, q, ldq, (const void *)nullptr, ldk, (const void *)nullptr, ldvt, o, ldo, 0, 0, 0, \
+                           Hq, Hkv, 1, (int64_t)0, layer_k_off, layer_v_off, (int64_t)0, seqs_dev);                                                                   \
+        break;
+        FA2_SEQS(64)
+        FA2_SEQS(128)
+#undef FA2_SEQS
+    default: return MLLM_HIP_ERR_SHAPE;
+    }
+    return MH_LAUNCH_OK("fa2_prefill_seqs");
+}
 }  // namespace mllm_hip
 
 using namespace mllm_hip;
@@ -492,7 +567,7 @@ static int launch_fa2(const float *Q, int64_t ldq, const void *K, int64_t ldk, c
     const int sk_eff = Tc * 4 + left;
     constexpr int R = FA_R;
     hipLaunchKernelGGL((fa2_prefill_kernel<D, F16, VT>), dim3((Sq + R - 1) / R, Hq, nbatch), dim3(256), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Sq, Sk, sk_eff, Hq,
-                       Hkv, causal, bq, bk, bv, bo);
+                       Hkv, causal, bq, bk, bv, bo, (const PrefillSeq *)nullptr);
     return MH_LAUNCH_OK("fa2_prefill");
 }
 

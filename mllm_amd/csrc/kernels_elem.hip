@@ -636,6 +636,16 @@ __global__ __launch_bounds__(1024) void seqs_next_kernel(SeqKV *__restrict__ seq
         ctl->n_active = n;
     }
 }
+// wave w folds row w's partial maxima (std::max_element: first maximum) -> out[w]; one workgroup, B <= 16 waves: seqs_next_kernel's fold without a state to advance
+__global__ __launch_bounds__(1024) void argmax_final_rows_kernel(const float *__restrict__ part_val, const int *__restrict__ part_idx, int nparts, int B, int *__restrict__ out) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (w >= B) return;
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+    for (int i = lane; i < nparts; i += 64) first_max_merge(best, besti, part_val[(int64_t)w * nparts + i], part_idx[(int64_t)w * nparts + i]);
+    wave_first_max(best, besti);
+    if (lane == 0) out[w] = besti;
+}
 __global__ __launch_bounds__(64) void argmax_final_kernel(const float *__restrict__ part_val, const int *__restrict__ part_idx, int nparts, int *__restrict__ out) {
     float best = -INFINITY;
     int besti = 0x7fffffff;
@@ -827,6 +837,46 @@ __global__ __launch_bounds__(256) void seqs_rope_append_kernel(float *__restrict
             vout[(int64_t)c * ldv] = f2h(row[(Hq + Hkv) * D + c]);
         }
     }
+}
+// the same for the prompts of B sequences concatenated row after row (batched prefill): blockIdx.y = sequence, whose rows [row0, row0 + S), cache position T0 and slabs come
+// from its descriptor; row r of the buffers takes row r of the (concatenated) table -- qkv_rope_append_kernel's arithmetic, element for element.  The host has checked
+// T0 + S <= the slabs' capacity.
+__global__ __launch_bounds__(256) void prefill_seqs_rope_append_kernel(float *__restrict__ qkv, int64_t ldq, const float *__restrict__ sin_t, const float *__restrict__ cos_t,
+                                                                       int ld_tab, const PrefillSeq *__restrict__ seqs, int64_t layer_k_off, int64_t layer_v_off, int64_t ldk,
+                                                                       int64_t ldv, int Hq, int Hkv, int D) {
+    const PrefillSeq sq = seqs[blockIdx.y];
+    const int S = sq.S, half = D >> 1;
+    if (S <= 0 || sq.T0 < 0) return;
+    qkv += (int64_t)sq.row0 * ldq;
+    sin_t += (int64_t)sq.row0 * ld_tab;
+    cos_t += (int64_t)sq.row0 * ld_tab;
+    uint16_t *kout = sq.k + layer_k_off + (int64_t)sq.T0 * ldk, *vout = sq.v + layer_v_off + sq.T0;
+    const int64_t nq = (int64_t)S * Hq * half, nk = (int64_t)S * Hkv * half, nv = (int64_t)S * Hkv * D;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nq + nk + nv; t += (int64_t)gridDim.x * 256) {
+        if (t < nq + nk) {
+            const bool isk = t >= nq;
+            const int64_t u = isk ? t - nq : t;
+            const int H = isk ? Hkv : Hq;
+            const int d = (int)(u % half), h = (int)((u / half) % H), s_ = (int)(u / ((int64_t)half * H));
+            float *x = qkv + (int64_t)s_ * ldq + (isk ? Hq * D : 0) + h * D + d;
+            const float a = x[0], b = x[half];
+            const float sv = sin_t[(int64_t)s_ * ld_tab + d], cv = cos_t[(int64_t)s_ * ld_tab + d];
+            float v1, v2;
+            rope_pair(a, b, sv, cv, v1, v2);
+            if (isk) { uint16_t *o = kout + (int64_t)s_ * ldk + h * D + d; o[0] = f2h(v1); o[half] = f2h(v2); }
+            else { x[0] = v1; x[half] = v2; }
+        } else {
+            const int64_t u = t - nq - nk;
+            const int c = (int)(u / S), s_ = (int)(u % S);
+            vout[(int64_t)c * ldv + s_] = f2h(qkv[(int64_t)s_ * ldq + (Hq + Hkv) * D + c]);
+        }
+    }
+}
+// dst[b][:] = src[rows[b]][:]: the last row of every sequence of a batched prefill, gathered for the final norm and the head
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, const int *__restrict__ rows, float *__restrict__ dst, int dim) {
+    const float4 *in = reinterpret_cast<const float4 *>(src + (int64_t)rows[blockIdx.x] * dim);
+    float4 *out = reinterpret_cast<float4 *>(dst + (int64_t)blockIdx.x * dim);
+    for (int i = threadIdx.x; i < dim / 4; i += 256) out[i] = in[i];
 }
 __global__ __launch_bounds__(256) void store_f16_kernel(const float *__restrict__ x, int64_t ldx, uint16_t *__restrict__ out, int64_t ldo, int S, int n) {
     const int64_t total = (int64_t)S * n;
@@ -1239,6 +1289,30 @@ int seqs_argmax_next_launch(const float *logits, int64_t ld_logits, int vocab, i
     if (int rc = MH_LAUNCH_OK("argmax_parts_rows")) return rc;
     hipLaunchKernelGGL(seqs_next_kernel, dim3(1), dim3(1024), 0, st, seqs_dev, ctl, part_val, part_idx, nparts, B, tok_out, ids_f, history, hist_ld);
     return MH_LAUNCH_OK("seqs_next");
+}
+int prefill_seqs_rope_append_launch(float *qkv, int64_t ldq, const float *sin_t, const float *cos_t, int ld_tab, const PrefillSeq *seqs_dev, int64_t layer_k_off,
+                                    int64_t layer_v_off, int64_t ldk, int64_t ldvt, int B, int max_S, int Hq, int Hkv, int D, hipStream_t st) {
+    if (B <= 0 || max_S <= 0) return MLLM_HIP_OK;
+    if (D <= 0 || D % 2 || Hq <= 0 || Hkv <= 0 || ldq < (int64_t)(Hq + 2 * Hkv) * D || B > 65535) return MLLM_HIP_ERR_SHAPE;
+    if (!qkv || !seqs_dev || !sin_t || !cos_t) return MLLM_HIP_ERR_ARG;
+    const int64_t n = (int64_t)max_S * (Hq + Hkv) * (D / 2) + (int64_t)max_S * Hkv * D;
+    hipLaunchKernelGGL(prefill_seqs_rope_append_kernel, dim3(grid_for(n, 256), B), dim3(256), 0, st, qkv, ldq, sin_t, cos_t, ld_tab, seqs_dev, layer_k_off, layer_v_off, ldk, ldvt,
+                       Hq, Hkv, D);
+    return MH_LAUNCH_OK("prefill_seqs_rope_append");
+}
+int gather_rows_launch(const float *src, const int *rows_dev, float *dst, int B, int dim, hipStream_t st) {
+    if (B <= 0) return MLLM_HIP_OK;
+    if (!src || !rows_dev || !dst) return MLLM_HIP_ERR_ARG;
+    if (dim <= 0 || dim % 4) return MLLM_HIP_ERR_SHAPE;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, st, src, rows_dev, dst, dim);
+    return MH_LAUNCH_OK("gather_rows");
+}
+int rows_argmax_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, int *tok_out, hipStream_t st) {
+    if (!logits || !part_val || !part_idx || !tok_out || B < 1 || B > 16 || nparts < 1 || vocab < 1) return MLLM_HIP_ERR_ARG;
+    hipLaunchKernelGGL(argmax_parts_rows_kernel, dim3(nparts, B), dim3(256), 0, st, logits, ld_logits, vocab, part_val, part_idx);
+    if (int rc = MH_LAUNCH_OK("argmax_parts_rows")) return rc;
+    hipLaunchKernelGGL(argmax_final_rows_kernel, dim3(1), dim3(1024), 0, st, part_val, part_idx, nparts, B, tok_out);
+    return MH_LAUNCH_OK("argmax_final_rows");
 }
 }  // namespace mllm_hip
 extern "C" int mllm_hip_store_f16(const float *x, int64_t ldx, uint16_t *out, int64_t ldo, int S, int n, void *stream) {

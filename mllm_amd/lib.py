@@ -262,6 +262,24 @@ class Model:
         check(load().mllm_hip_model_batch_generate(self._h, C.c_int(B), vp(t), C.c_int(int(steps)), C.c_int32(int(eos)), vp(toks), vp(n), C.byref(ms)), "batch_generate")
         return toks, n, ms.value
 
+    def batch_prefill(self, prompts, visual_dev=None, grid_thw=None, n_visual_rows=None, want_logits=True):
+        """The prompts of sequences 0 .. len(prompts) - 1 in one pass over the weights (each appended to its own cache): (next greedy ids [B], logits [B][vocab] or None,
+        device ms).  Image prompts (Qwen2-VL): visual_dev = device tensor / pointer of the tower's output rows of the image prompts one after the other (Model.vision),
+        grid_thw = the grid they share, n_visual_rows[b] = 0 for a text prompt."""
+        ps = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        B = len(ps)
+        n = np.array([p.size for p in ps], dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate(ps), dtype=np.int32) if B else np.zeros(0, dtype=np.int32)
+        meta = np.ascontiguousarray(grid_thw, dtype=np.int32) if grid_thw is not None else None
+        nvr = np.ascontiguousarray(n_visual_rows, dtype=np.int32) if n_visual_rows is not None else None
+        if nvr is not None and nvr.size != B:
+            raise ValueError("n_visual_rows must hold one count per prompt")
+        nxt = np.empty(B, dtype=np.int32)
+        lg = np.empty((B, self.vocab), dtype=np.float32) if want_logits else None
+        ms = C.c_float()
+        check(load().mllm_hip_model_batch_prefill(self._h, C.c_int(B), vp(ids), vp(n), vp(visual_dev), vp(meta), vp(nvr), vp(lg), vp(nxt), C.byref(ms)), "batch_prefill")
+        return nxt, lg, ms.value
+
     def cache_len(self) -> int:
         """Tokens the KV cache holds (0 on a fresh or cleared model)."""
         return int(load().mllm_hip_model_cache_len(self._h))
