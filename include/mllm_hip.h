@@ -217,6 +217,20 @@ int mllm_hip_sort_desc(const float *x, int n, float *val_sorted, int *idx_sorted
 /* the draw of both sampling methods, _sample_element (mllm/Generate.hpp:38-44: std::discrete_distribution over the float probabilities), as an
  * inverse CDF on a caller-supplied uniform number u01 in [0,1): returns the index of the drawn candidate (host arithmetic). */
 int mllm_hip_sample_index_host(const float *probs, int k, float u01);
+/* Both sampling methods for `rows` rows of scores in device memory (row pitch ld >= n), entirely on the device: replaces mllm/Generate.cpp:45-142 and the draw of
+ * Generate.hpp:38-44 for a batch.  Per row: the candidates -- method 1: the top_k <= 64 largest in mllm_hip_topk's order (top_k = 0 or 1: the first-maximum argmax,
+ * Generate.cpp:50-54); method 2: softmax_first != 0 runs mllm_hip_softmax over the row first (0: the row already holds probabilities), then mllm_hip_sort_desc's
+ * order and the prefix kept by `while (p < top_p) p += val[n++]` in float (:108-115), which may be the whole row --, then mllm_hip_topk_probs_host's probabilities bit
+ * for bit (sequential double sums, the exp()s spread over lanes), then mllm_hip_sample_index_host's draw on u01[row]; ids_out[row] = the drawn candidate's index.
+ * The double exp is the device library's (<= 1 ulp) where the host function uses libm's: *n_ambiguous (device, may be NULL; the caller zeroes it) is incremented for
+ * every candidate whose exp lies within 2 double ulps of a float rounding tie -- outside that band both round to the same float, inside nothing is claimed (about
+ * 2^-26 per candidate).  Optional outputs for tests (device, may be NULL): row r's candidate indices / probabilities at cand_idx / cand_prob + r * cand_ld
+ * (cand_ld >= top_k, or >= n for method 2) and their count in cand_n[r].  u01, ids_out: device, [rows].  workspace: mllm_hip_sample_rows_workspace_bytes() bytes of
+ * device memory; nothing is allocated inside, so the call can be captured into a graph. */
+size_t mllm_hip_sample_rows_workspace_bytes(int rows, int n, int method, int top_k);
+int mllm_hip_sample_rows(const float *x, int64_t ld, int rows, int n, int method, int top_k, float top_p, float temperature, int softmax_first, const float *u01,
+                         int *ids_out, int *cand_idx, float *cand_prob, int64_t cand_ld, int *cand_n, int *n_ambiguous, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* ---- A10/A11/A19: rotary embeddings. Tables are built on the host with the reference's libm formulas
  *      (CPURoPE.cpp:22-31,100-128; CPUMultimodalRoPE.cpp:26-36,84-118,37-82; CPUVisionRoPE.cpp:19-55) and uploaded;
@@ -383,6 +397,16 @@ int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens,
  * side of the steps) may be NULL.  ERR_ARG: NULL model / first_tokens, no LLM, B < 1 or above batch_begin's, steps <= 0, a sequence without a prefill; ERR_SHAPE:
  * cache_len[b] + steps > cache_limit for some b (nothing changed).  After a failure inside the loop the host's counters are re-read from the device state. */
 int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out, float *elapsed_ms);
+/* mllm_hip_model_batch_generate with Module::generate's three methods (mllm/Generate.cpp:45-142, the draw of Generate.hpp:38-44): 0 greedy (batch_generate's step
+ * unchanged; so is method 1 with top_k 0 or 1), 1 top-k, 2 top-p over the softmax of the logit row.  The sampled tail of the step is mllm_hip_sample_rows on the B logit
+ * rows plus the state advance on the drawn ids, in the same captured step: nothing crosses PCIe between steps.  One set of parameters for the whole batch.  Row b's
+ * s-th step draws on u01[b * steps + s] (host, [B][steps], in [0,1)); a row that has stopped draws nothing.  Row b equals, id for id, what
+ * mllm_hip_model_generate_sampled produces for sequence b alone with u01 + b * steps, provided *n_ambiguous (may be NULL) comes back 0: it counts the candidates whose
+ * double exp lay within 2 ulps of a float rounding tie (see mllm_hip_sample_rows).  tokens_host / n_out / eos / the caches afterwards: as for batch_generate.
+ * ERR_ARG / ERR_SHAPE, before anything runs and with nothing changed: generate_sampled's rules (method outside 0..2; methods 1, 2: u01 NULL, temperature <= 0 or NaN;
+ * top_k outside 0..64 or above vocab; top_p <= 0 or NaN) and batch_generate's. */
+int mllm_hip_model_batch_generate_sampled(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int method, int top_k, float top_p, float temperature,
+                                          const float *u01, int32_t eos, int32_t *tokens_host, int32_t *n_out, int32_t *n_ambiguous, float *elapsed_ms);
 /* Batched prefill: the prompts of sequences 0 .. B-1 of batch_begin in ONE pass over the weights, instead of B times batch_select + mllm_hip_model_prefill (the
  * reference's hook: KVCache_batch, mllm/Types.hpp:26-33; the forward the demos run over the prompt, examples/demo_qwen2_vl.cpp:53-63, demo_qwen.cpp, demo_tinyllama.cpp).
  * `ids` holds the B prompts concatenated, n_ids[b] the length of prompt b; sequence b's rows are appended to ITS cache behind the cache_len[b] tokens it already holds

@@ -125,6 +125,35 @@ int seqs_fa2_decode_launch(const float *q, int64_t ldq, const SeqKV *seqs_dev, i
 int seqs_argmax_next_launch(const float *logits, int64_t ld_logits, int vocab, int B, float *part_val, int *part_idx, int nparts, SeqKV *seqs_dev, BatchCtl *ctl, int *tok_out,
                             float *ids_f, int *history, int hist_ld, hipStream_t st);
 
+// ---- batched sampling (kernels_sample.hip; engine.hip: mllm_hip_model_batch_generate_sampled): the sampled tail of a B-row step ----
+// what a captured sampled step reads from device memory, so that another nucleus mass, temperature or number of steps needs no re-capture
+struct SampleCtl {
+    float top_p, temperature;
+    int u_ld;            // uniform numbers per row of u01 (the call's steps)
+    int n_ambiguous;     // candidates whose exp() lay within 2 double ulps of a float rounding tie (ref_arith.h f32_rounding_ambiguous): the engine's counter, which
+                         // it hands to the launcher as SampleRows::n_ambiguous like any other caller
+};
+// mllm_hip_sample_rows (include/mllm_hip.h) with everything a captured step needs: ctl != nullptr: top_p / temperature / u_ld are read from it (and from nowhere else);
+// n_ambiguous is the one counter the kernels add to (nullptr: none); seqs != nullptr: row b draws on u01[b * u_ld + made_b], and a row that has stopped or whose cache is
+// full (t >= cap) draws nothing.
+struct SampleRows {
+    const float *x; int64_t ld; int rows, n, method, top_k, softmax_first;
+    float top_p, temperature; const SampleCtl *ctl;
+    const float *u01; const SeqKV *seqs; int cap;
+    int *ids_out; int *cand_idx; float *cand_prob; int64_t cand_ld; int *cand_n; int *n_ambiguous;
+    void *ws; size_t ws_bytes;
+};
+size_t sample_rows_workspace_bytes(int rows, int n, int method, int top_k);
+int sample_rows_launch(const SampleRows &a, hipStream_t st);
+// seqs_next_kernel with the drawn id in place of the folded argmax: drawn[b] -> tok_out[b], history[b][made_b], ids_f[b]; t / pos / made of the active rows advance,
+// `active` is cleared on the end-of-sequence id, BatchCtl::n_active counted.  A row whose cache is full (t >= cap) is left alone, like a stopped one.
+int seqs_sample_next_launch(const int *drawn, int B, int cap, SeqKV *seqs_dev, BatchCtl *ctl, int *tok_out, float *ids_f, int *history, int hist_ld, hipStream_t st);
+// kernels_elem.hip, rows in blockIdx.y, scratch from the caller (capturable): the k best of every row in mllm_hip_topk's order; the long-row softmax of mllm_hip_softmax
+size_t rows_topk_scratch_bytes(int rows, int n, int k);
+int rows_topk_launch(const float *x, int64_t ld, int rows, int n, int k, float *out_val, int *out_idx, int ldo, void *scr, hipStream_t st);
+size_t softmax_long_rows_scratch_bytes(int rows, int n);
+int softmax_long_rows_launch(const float *x, int64_t ldx, float *y, int64_t ldy, int rows, int n, float *scr, hipStream_t st);
+
 // ---- batched prefill (engine.hip: mllm_hip_model_batch_prefill): the prompts of B sequences sit concatenated, sequence after sequence, in the activation buffers ----
 // One sequence's share of the pass.  The host knows every length, fills the array and uploads it once per call; the kernels read it from device memory.
 struct PrefillSeq {

@@ -242,6 +242,10 @@ struct mllm_hip_model {
     // of a batch_generate [batch_cap][cache_limit]; its captured step (one live graph, for bgraph_B rows; a B is captured once a step of that B has run eagerly)
     float *btab_sin = nullptr, *btab_cos = nullptr; BatchCtl *bctl = nullptr; int *bhist = nullptr;
     hipGraph_t bgraph = nullptr; hipGraphExec_t bgraph_exec = nullptr; int bgraph_B = 0; unsigned beager = 0;
+    // batch_generate_sampled: the live graph's tail (0 = the argmax tail, else method << 8 | top_k), the B's whose sampled tail of a method has run eagerly once, and the
+    // tail's device memory -- workspace of mllm_hip_sample_rows, the call's uniform numbers [B][steps], the control words, the drawn ids [batch_cap]
+    int bgraph_tail = 0; unsigned beager_tail[3] = {0, 0, 0};
+    void *bs_ws = nullptr; size_t bs_ws_bytes = 0; float *bs_u01 = nullptr; size_t bs_u01_elems = 0; SampleCtl *bs_ctl = nullptr; int *bs_drawn = nullptr; int bs_drawn_cap = 0;
     int64_t decode_weight_bytes = 0, resident_bytes = 0, released_bytes = 0;      // device bytes held after the load / raw rows and packs not kept (load_linear_q4k)
     float load_total_ms = 0, load_h2d_ms = 0, load_tail_ms = 0;
 
@@ -601,6 +605,8 @@ extern "C" void mllm_hip_model_destroy(mllm_hip_model *m) {
     for (void *p : m->temps) (void)hipFree(p);
     if (m->xpack) (void)hipFree(m->xpack);
     if (m->sort_ws) (void)hipFree(m->sort_ws);
+    if (m->bs_ws) (void)hipFree(m->bs_ws);
+    if (m->bs_u01) (void)hipFree(m->bs_u01);
     if (m->pin_img) (void)hipHostFree(m->pin_img);
     m->ld.destroy();
     for (int b = 0; b < 2; ++b) { if (m->vup[b]) (void)hipEventDestroy(m->vup[b]); if (m->vfree[b]) (void)hipEventDestroy(m->vfree[b]); }
@@ -1203,7 +1209,7 @@ static int drop_batch_graph(M *m) {
         HH(hipGraphExecDestroy(m->bgraph_exec)); m->bgraph_exec = nullptr;
     }
     if (m->bgraph) { HH(hipGraphDestroy(m->bgraph)); m->bgraph = nullptr; }
-    m->bgraph_B = 0;
+    m->bgraph_B = 0; m->bgraph_tail = 0;
     return 0;
 }
 extern "C" int mllm_hip_model_batch_begin(mllm_hip_model *m, int B) {
@@ -1284,7 +1290,13 @@ static int batch_upload_state(M *m, int B, const int32_t *tokens, int32_t eos) {
 // The launches of one batched step, all on the engine's stream and each a plain dependent launch: the row-wise Ops of the prefill's per-Op launchers over B rows, per
 // layer the rotary + cache append and the attention of all B sequences (one launch each, the sequences' slabs / positions read from their device state), the head, then
 // the B argmaxes in one launch and the fold that advances the device state.  batch_decode issues it eagerly, batch_generate replays it as a captured graph.
-static int batch_step_body(M *m, int B) {
+// tail != nullptr (batch_generate_sampled, methods 1 and 2): the B logit rows go through the sampled tail instead -- candidate selection, candidate softmax and draw on
+// the device (kernels_sample.hip), then the same state advance on the drawn ids.
+namespace {
+struct SampledTail { int method, top_k; };
+inline int tail_key(const SampledTail *t) { return t ? (t->method << 8 | t->top_k) : 0; }
+}  // namespace
+static int batch_step_body(M *m, int B, const SampledTail *tail = nullptr) {
     const auto &c = m->c;
     const int H = c.hidden, I = c.inter, D = m->D, half = D / 2;
     hipStream_t st = m->st;
@@ -1316,6 +1328,15 @@ static int batch_step_body(M *m, int B) {
     } else {
         EH(mllm_hip_rmsnorm(h, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, B, H, c.final_eps, 0, st));
         EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->blogits, MLLM_HIP_F32, c.vocab, nullptr, B, c.vocab, H, st));
+    }
+    if (tail) {
+        SampleRows a{};
+        a.x = m->blogits; a.ld = c.vocab; a.rows = B; a.n = c.vocab; a.method = tail->method; a.top_k = tail->top_k;
+        a.softmax_first = 1;      // top-p works on probabilities: the vocabulary softmax the caller's graph ends in, as in generate_sampled
+        a.ctl = m->bs_ctl; a.u01 = m->bs_u01; a.seqs = m->seqkv_dev; a.cap = c.cache_limit;
+        a.ids_out = m->bs_drawn; a.n_ambiguous = &m->bs_ctl->n_ambiguous; a.ws = m->bs_ws; a.ws_bytes = m->bs_ws_bytes;
+        EH(sample_rows_launch(a, st));
+        return seqs_sample_next_launch(m->bs_drawn, B, c.cache_limit, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
     }
     const int np = std::max(1, std::min(m->max_parts / B, 128));
     return seqs_argmax_next_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
@@ -1357,22 +1378,24 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
 
 // One step of batch_generate.  The first step of a given B on this model runs eagerly (the Ops' one-time work -- growing the GEMM's activation scratch, function
 // attributes -- must not sit inside a capture); from the second on the step is one captured graph, a single chain on the engine's stream, re-captured when B changes.
-static int batch_step(M *m, int B) {
+// A sampled tail follows the same rule per (B, method), and the live graph is also re-captured when the tail (method, top_k) changes.
+static int batch_step(M *m, int B, const SampledTail *tail = nullptr) {
     const unsigned bit = 1u << B;
-    if (!m->use_graph || !(m->beager & bit)) {
-        EH(batch_step_body(m, B));
+    if (!m->use_graph || !(m->beager & bit) || (tail && !(m->beager_tail[tail->method] & bit))) {
+        EH(batch_step_body(m, B, tail));
         m->beager |= bit;
+        if (tail) m->beager_tail[tail->method] |= bit;
         return 0;
     }
-    if (m->bgraph_B != B) {
+    if (m->bgraph_B != B || m->bgraph_tail != tail_key(tail)) {
         EH(drop_batch_graph(m));
         HH(hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal));
-        const int rc = batch_step_body(m, B);
+        const int rc = batch_step_body(m, B, tail);
         const hipError_t e = hipStreamEndCapture(m->st, &m->bgraph);
         if (rc) { (void)drop_batch_graph(m); return rc; }
         HH(e);
         HH(hipGraphInstantiate(&m->bgraph_exec, m->bgraph, nullptr, nullptr, 0));
-        m->bgraph_B = B;
+        m->bgraph_B = B; m->bgraph_tail = tail_key(tail);
     }
     HH(hipGraphLaunch(m->bgraph_exec, m->st));
     return 0;
@@ -1391,16 +1414,13 @@ static int batch_read_state(M *m, int B, std::vector<SeqKV> &desc) {
     if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
     return 0;
 }
-extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out,
-                                             float *elapsed_ms) {
-    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0) return MLLM_HIP_ERR_ARG;
-    EH(batch_check(m, B, steps, "mllm_hip_model_batch_generate"));
+// the loop of both batch_generate entry points: state uploaded -> `steps` steps (fewer once every row has stopped) -> the host's counters re-read from the device state
+static int batch_generate_loop(M *m, int B, int steps, int32_t eos, const SampledTail *tail, std::vector<SeqKV> &desc) {
     constexpr int EOS_CHECK_EVERY = 16;      // steps between two reads of BatchCtl::n_active (4 bytes, one synchronisation); a stopped batch overruns by fewer steps, which change nothing
-    EH(batch_upload_state(m, B, first_tokens, eos));
     auto run = [&]() -> int {
         HH(hipEventRecord(m->ev0, m->st));
         for (int s = 0; s < steps; ++s) {
-            EH(batch_step(m, B));
+            EH(batch_step(m, B, tail));
             if (eos >= 0 && (s + 1) % EOS_CHECK_EVERY == 0 && s + 1 < steps) {
                 int live = 0;
                 HH(hipStreamSynchronize(m->st));
@@ -1412,14 +1432,79 @@ extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int
         return 0;
     };
     const int rc = run();
-    std::vector<SeqKV> desc;
     const int rc2 = batch_read_state(m, B, desc);
-    if (rc) return rc;
-    EH(rc2);
+    return rc ? rc : rc2;
+}
+extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int32_t eos, int32_t *tokens_host, int32_t *n_out,
+                                             float *elapsed_ms) {
+    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0) return MLLM_HIP_ERR_ARG;
+    EH(batch_check(m, B, steps, "mllm_hip_model_batch_generate"));
+    EH(batch_upload_state(m, B, first_tokens, eos));
+    std::vector<SeqKV> desc;
+    EH(batch_generate_loop(m, B, steps, eos, nullptr, desc));
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
     if (n_out) for (int b = 0; b < B; ++b) n_out[b] = desc[b].made;
     if (tokens_host) {
         HH(hipMemcpy2D(tokens_host, (size_t)steps * 4, m->bhist, (size_t)m->c.cache_limit * 4, (size_t)steps * 4, B, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) for (int s = desc[b].made; s < steps; ++s) tokens_host[(size_t)b * steps + s] = -1;
+    }
+    return MLLM_HIP_OK;
+}
+// batch_generate with Module::generate's method switch (mllm/Generate.cpp:45-142): method 0 is batch_generate's step unchanged; methods 1 and 2 end the step in the
+// sampled tail (batch_step_body), so the candidates, the temperature softmax over them (Generate.cpp:69-87 / :120-136), the draw (Generate.hpp:38-44, as an inverse
+// CDF on u01[b][step of row b]) and the state advance all stay on the device: nothing crosses PCIe between steps.  What a call changes without a new graph -- top_p,
+// temperature, the uniform numbers, their row pitch -- is read from device memory (SampleCtl, bs_u01); B, method and top_k are launch shapes and re-capture.
+// Uploads and read-backs are staged in the page-locked block (ensure_batch_pin), never on the caller's pageable arrays.
+extern "C" int mllm_hip_model_batch_generate_sampled(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int method, int top_k, float top_p, float temperature,
+                                                     const float *u01, int32_t eos, int32_t *tokens_host, int32_t *n_out, int32_t *n_ambiguous, float *elapsed_ms) {
+    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0 || method < 0 || method > 2) return MLLM_HIP_ERR_ARG;
+    if (method != 0 && (!u01 || !(temperature > 0.0f))) return MLLM_HIP_ERR_ARG;
+    if (method == 1 && (top_k < 0 || top_k > 64 || top_k > m->c.vocab)) return MLLM_HIP_ERR_SHAPE;
+    if (method == 2 && !(top_p > 0.0f)) return MLLM_HIP_ERR_ARG;      // p <= 0 or NaN keeps no candidate at all (generate_sampled's rule)
+    EH(batch_check(m, B, steps, "mllm_hip_model_batch_generate_sampled"));
+    const auto &c = m->c;
+    // greedy, and top-k with k in {0, 1} (Generate.cpp:50-54), are the first-maximum argmax: batch_generate's tail
+    const bool sampled = method == 2 || (method == 1 && top_k > 1);
+    const SampledTail tail = {method, method == 1 ? top_k : 0};
+    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t n_u = (size_t)B * steps, o_ctl = up64(n_u * 4), o_hist = o_ctl + up64(sizeof(SampleCtl));
+    EH(ensure_batch_pin(m, o_hist + n_u * 4));
+    if (sampled) {
+        // the tail's device memory; whatever is replaced here is an address the live graph holds
+        const size_t ws_b = sample_rows_workspace_bytes(m->batch_cap, c.vocab, method, method == 1 ? 64 : 0);
+        if (ws_b > m->bs_ws_bytes) {
+            EH(drop_batch_graph(m));
+            if (m->bs_ws) HH(hipFree(m->bs_ws));
+            m->bs_ws = nullptr; m->bs_ws_bytes = 0;
+            HH(hipMalloc(&m->bs_ws, ws_b));
+            m->bs_ws_bytes = ws_b;
+        }
+        if (n_u > m->bs_u01_elems) {
+            EH(drop_batch_graph(m));
+            if (m->bs_u01) HH(hipFree(m->bs_u01));
+            m->bs_u01 = nullptr; m->bs_u01_elems = 0;
+            HH(hipMalloc((void **)&m->bs_u01, n_u * 4));
+            m->bs_u01_elems = n_u;
+        }
+        if (!m->bs_ctl) EH(m->dalloc(&m->bs_ctl, sizeof(SampleCtl)));
+        if (m->bs_drawn_cap < m->batch_cap) { EH(drop_batch_graph(m)); EH(m->dalloc(&m->bs_drawn, (size_t)m->batch_cap * 4)); m->bs_drawn_cap = m->batch_cap; }
+        memcpy(m->pf_pin, u01, n_u * 4);
+        const SampleCtl ctl = {top_p, temperature, steps, 0};
+        memcpy(m->pf_pin + o_ctl, &ctl, sizeof(ctl));
+        HH(hipMemcpyAsync(m->bs_u01, m->pf_pin, n_u * 4, hipMemcpyHostToDevice, m->st));
+        HH(hipMemcpyAsync(m->bs_ctl, m->pf_pin + o_ctl, sizeof(ctl), hipMemcpyHostToDevice, m->st));
+    }
+    EH(batch_upload_state(m, B, first_tokens, eos));      // synchronises: the inputs are resident when the clock starts
+    std::vector<SeqKV> desc;
+    EH(batch_generate_loop(m, B, steps, eos, sampled ? &tail : nullptr, desc));
+    if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
+    if (n_out) for (int b = 0; b < B; ++b) n_out[b] = desc[b].made;
+    if (tokens_host) HH(hipMemcpy2DAsync(m->pf_pin + o_hist, (size_t)steps * 4, m->bhist, (size_t)c.cache_limit * 4, (size_t)steps * 4, B, hipMemcpyDeviceToHost, m->st));
+    if (sampled) HH(hipMemcpyAsync(m->pf_pin + o_ctl, m->bs_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, m->st));
+    HH(hipStreamSynchronize(m->st));
+    if (n_ambiguous) *n_ambiguous = sampled ? reinterpret_cast<const SampleCtl *>(m->pf_pin + o_ctl)->n_ambiguous : 0;
+    if (tokens_host) {
+        memcpy(tokens_host, m->pf_pin + o_hist, n_u * 4);
         for (int b = 0; b < B; ++b) for (int s = desc[b].made; s < steps; ++s) tokens_host[(size_t)b * steps + s] = -1;
     }
     return MLLM_HIP_OK;

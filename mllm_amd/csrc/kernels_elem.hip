@@ -465,9 +465,11 @@ __global__ __launch_bounds__(64) void softmax_kernel(const float *__restrict__ x
 // ---- the same softmax for ONE long row (a vocabulary: top-p sampling), spread over the chip.  What is order-free runs everywhere -- the maximum, y = ref_expf_poly(x - max) and
 // the sum of every 8-chunk in its hsum order --; the row sum is still the reference's: the chunk sums added one after the other, then the trailing columns.  One wave does
 // that with a travelling accumulator (lane l holds 16 consecutive chunk sums, a wave_ror hop between lanes: ln_fused_kernel's walk): 19 k dependent adds instead of the
-// 1.9 ms the single-wave kernel above spends on a 151,936-wide row.
-__global__ __launch_bounds__(256) void softmax_row_max_kernel(const float *__restrict__ x, int n, float *__restrict__ part) {
+// 1.9 ms the single-wave kernel above spends on a 151,936-wide row.  blockIdx.y = row (pitches ldx / ldy; a row's partial maxima, chunk sums and 1 / sum sit at
+// its own offset of the scratch): the batched top-p step runs B vocabulary rows through the same four launches.
+__global__ __launch_bounds__(256) void softmax_row_max_kernel(const float *__restrict__ x, int64_t ldx, int n, float *__restrict__ part) {
     __shared__ float sv[4];
+    x += (int64_t)blockIdx.y * ldx; part += (int64_t)blockIdx.y * gridDim.x;
     float mx = -INFINITY;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) mx = fmaxf(mx, x[i]);
     mx = wave_max(mx);
@@ -475,10 +477,11 @@ __global__ __launch_bounds__(256) void softmax_row_max_kernel(const float *__res
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
 }
-__global__ __launch_bounds__(256) void softmax_row_exp_kernel(const float *__restrict__ x, float *__restrict__ y, int n, const float *__restrict__ part, int nparts,
-                                                              float *__restrict__ chunk_sums) {
+__global__ __launch_bounds__(256) void softmax_row_exp_kernel(const float *__restrict__ x, int64_t ldx, float *__restrict__ y, int64_t ldy, int n,
+                                                              const float *__restrict__ part, int nparts, float *__restrict__ chunk_sums) {
     __shared__ uint64_t tab[32];
     expf_tab_store(tab, expf_tab_fetch());
+    x += (int64_t)blockIdx.y * ldx; y += (int64_t)blockIdx.y * ldy; part += (int64_t)blockIdx.y * nparts; chunk_sums += (int64_t)blockIdx.y * (n >> 3);
     float mx = -INFINITY;
     for (int i = 0; i < nparts; ++i) mx = fmaxf(mx, part[i]);
     __syncthreads();
@@ -494,8 +497,10 @@ __global__ __launch_bounds__(256) void softmax_row_exp_kernel(const float *__res
     }
 }
 constexpr int DPP_WAVE_ROR1_SM = 0x13C;
-__global__ __launch_bounds__(64) void softmax_row_sum_kernel(const float *__restrict__ chunk_sums, int nchunks, const float *__restrict__ y, int n, float *__restrict__ inv_out) {
+__global__ __launch_bounds__(64) void softmax_row_sum_kernel(const float *__restrict__ chunk_sums, int nchunks, const float *__restrict__ y, int64_t ldy, int n,
+                                                             float *__restrict__ inv_out) {
     const int lane = threadIdx.x;
+    chunk_sums += (int64_t)blockIdx.y * nchunks; y += (int64_t)blockIdx.y * ldy; inv_out += blockIdx.y;
     float acc = 0.0f;
     for (int base = 0; base < nchunks; base += 1024) {
         float u[16];
@@ -512,8 +517,9 @@ __global__ __launch_bounds__(64) void softmax_row_sum_kernel(const float *__rest
     for (int i = n & ~7; i < n; ++i) sum = __fadd_rn(sum, y[i]);
     if (lane == 0) *inv_out = __fdiv_rn(1.0f, sum);
 }
-__global__ __launch_bounds__(256) void softmax_row_scale_kernel(float *__restrict__ y, int n, const float *__restrict__ inv) {
-    const float s = *inv;
+__global__ __launch_bounds__(256) void softmax_row_scale_kernel(float *__restrict__ y, int64_t ldy, int n, const float *__restrict__ inv) {
+    const float s = inv[blockIdx.y];
+    y += (int64_t)blockIdx.y * ldy;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) y[i] = __fmul_rn(y[i], s);
 }
 
@@ -1058,21 +1064,30 @@ extern "C" int mllm_hip_mul(const float *a, const float *b, float *y, int64_t n,
     hipLaunchKernelGGL(binary_kernel<1>, dim3(grid_for(n, 1024)), dim3(256), 0, as_stream(stream), a, b, y, n);
     return MH_LAUNCH_OK("mul");
 }
+namespace mllm_hip {
+// the long-row softmax of `rows` rows in four launches; scr: softmax_long_rows_scratch_bytes(rows, n) bytes of device memory the caller owns (nothing is allocated
+// here, so the launches can sit in a captured step)
+constexpr int SOFTMAX_ROW_NP = 128;
+size_t softmax_long_rows_scratch_bytes(int rows, int n) { return (size_t)rows * ((size_t)SOFTMAX_ROW_NP + 4 + (n >> 3)) * 4; }
+int softmax_long_rows_launch(const float *x, int64_t ldx, float *y, int64_t ldy, int rows, int n, float *scr, hipStream_t st) {
+    constexpr int NP = SOFTMAX_ROW_NP;
+    const int nchunks = n >> 3;
+    float *part = scr, *inv = scr + (size_t)rows * NP, *cs = inv + (((size_t)rows + 3) & ~(size_t)3);
+    hipLaunchKernelGGL(softmax_row_max_kernel, dim3(NP, rows), dim3(256), 0, st, x, ldx, n, part);
+    int rc = MH_LAUNCH_OK("softmax_row_max");
+    if (!rc) { hipLaunchKernelGGL(softmax_row_exp_kernel, dim3(grid_for(n, 256), rows), dim3(256), 0, st, x, ldx, y, ldy, n, (const float *)part, NP, cs); rc = MH_LAUNCH_OK("softmax_row_exp"); }
+    if (!rc) { hipLaunchKernelGGL(softmax_row_sum_kernel, dim3(1, rows), dim3(64), 0, st, (const float *)cs, nchunks, (const float *)y, ldy, n, inv); rc = MH_LAUNCH_OK("softmax_row_sum"); }
+    if (!rc) { hipLaunchKernelGGL(softmax_row_scale_kernel, dim3(grid_for(n, 256), rows), dim3(256), 0, st, y, ldy, n, (const float *)inv); rc = MH_LAUNCH_OK("softmax_row_scale"); }
+    return rc;
+}
+}  // namespace mllm_hip
 extern "C" int mllm_hip_softmax(const float *x, float *y, int rows, int n, const int *valid, void *stream) {
     if (rows <= 0) return MLLM_HIP_OK;
     hipStream_t st = as_stream(stream);
     if (rows == 1 && !valid && n >= 16384) {      // one long row: the order-free parts over the chip, the row sum by one wave (same bits as softmax_kernel)
-        constexpr int NP = 128;
-        const int nchunks = n >> 3;
         float *scr = nullptr;
-        MH_CHECK(hipMallocAsync((void **)&scr, ((size_t)NP + 4 + nchunks) * 4, st));
-        float *part = scr, *inv = scr + NP, *cs = scr + NP + 4;
-        int rc = MLLM_HIP_OK;
-        hipLaunchKernelGGL(softmax_row_max_kernel, dim3(NP), dim3(256), 0, st, x, n, part);
-        rc = MH_LAUNCH_OK("softmax_row_max");
-        if (!rc) { hipLaunchKernelGGL(softmax_row_exp_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, x, y, n, (const float *)part, NP, cs); rc = MH_LAUNCH_OK("softmax_row_exp"); }
-        if (!rc) { hipLaunchKernelGGL(softmax_row_sum_kernel, dim3(1), dim3(64), 0, st, (const float *)cs, nchunks, (const float *)y, n, inv); rc = MH_LAUNCH_OK("softmax_row_sum"); }
-        if (!rc) { hipLaunchKernelGGL(softmax_row_scale_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, y, n, (const float *)inv); rc = MH_LAUNCH_OK("softmax_row_scale"); }
+        MH_CHECK(hipMallocAsync((void **)&scr, softmax_long_rows_scratch_bytes(1, n), st));
+        int rc = softmax_long_rows_launch(x, n, y, n, 1, n, scr, st);
         const hipError_t e = hipFreeAsync(scr, st);
         if (e != hipSuccess && !rc) { set_error("hipFreeAsync", e, __FILE__, __LINE__); rc = MLLM_HIP_ERR_HIP; }
         return rc;
@@ -1138,17 +1153,20 @@ namespace mllm_hip {
 // the same selection over a slice, and over candidates that carry their own ids (ids == nullptr: the position is the id): workgroup b takes positions
 // [b * per, (b + 1) * per) and leaves its k best as (value, id), best first; slots it cannot fill get id 0x7fffffff, which no later stage accepts as a candidate.
 // The k best of the row are among the k best of every slice, and both stages order equal values by ascending id, so two stages select what the single workgroup does.
+// blockIdx.y = row: row r's values (and ids) start at r * ldx, its slices' results at r * ldo (the batched sampling step, rows_topk_launch; one row: ldx = ldo = 0).
 template <int NT>
-__global__ __launch_bounds__(NT) void topk_slice_kernel(const float *__restrict__ x, const int *__restrict__ ids, int n, int per, int k, float *__restrict__ out_val,
-                                                        int *__restrict__ out_idx) {
+__global__ __launch_bounds__(NT) void topk_slice_kernel(const float *__restrict__ x, const int *__restrict__ ids, int64_t ldx, int n, int per, int k,
+                                                        float *__restrict__ out_val, int *__restrict__ out_idx, int64_t ldo) {
     // the slice's values live in LDS for the k rounds; a selected value is replaced by NaN (never a candidate), as is the value of an unfilled slot of the stage before
     extern __shared__ __attribute__((aligned(16))) char tk_smem[];
     float *vals = reinterpret_cast<float *>(tk_smem);      // [per]
     __shared__ float sv[NT / 64];
     __shared__ int si[NT / 64], sp[NT / 64];
     const int lo = blockIdx.x * per, cnt = max(0, min(n, lo + per) - lo);
-    float *ov_ = out_val + (int64_t)blockIdx.x * k;
-    int *oi_ = out_idx + (int64_t)blockIdx.x * k;
+    x += (int64_t)blockIdx.y * ldx;
+    if (ids) ids += (int64_t)blockIdx.y * ldx;
+    float *ov_ = out_val + (int64_t)blockIdx.y * ldo + (int64_t)blockIdx.x * k;
+    int *oi_ = out_idx + (int64_t)blockIdx.y * ldo + (int64_t)blockIdx.x * k;
     for (int i = threadIdx.x; i < cnt; i += NT) vals[i] = (ids && ids[lo + i] == 0x7fffffff) ? __int_as_float(0x7fc00000) : x[lo + i];
     __syncthreads();
     for (int r = 0; r < k; ++r) {
@@ -1178,6 +1196,27 @@ __global__ __launch_bounds__(NT) void topk_slice_kernel(const float *__restrict_
         __syncthreads();
     }
 }
+// The k best of each of `rows` rows in one launch set (rows in blockIdx.y): rows of up to 8192 values by one workgroup each, longer ones (a vocabulary) in
+// mllm_hip_topk's two stages.  Row r's (value, index) pairs land at out_val / out_idx + r * ldo, best first.  scr: rows_topk_scratch_bytes() of the caller's
+// device memory -- nothing is allocated here, so the launches can sit in a captured step.  1 <= k <= 64, k <= n <= 128 * 8192.
+constexpr int TOPK_NP = 128, TOPK_ONE_WG = 8192;
+size_t rows_topk_scratch_bytes(int rows, int n, int k) { return n <= TOPK_ONE_WG ? 0 : (size_t)rows * TOPK_NP * k * 8; }
+int rows_topk_launch(const float *x, int64_t ld, int rows, int n, int k, float *out_val, int *out_idx, int ldo, void *scr, hipStream_t st) {
+    if (n <= 0 || k <= 0 || k > 64 || k > n || ldo < k || n > TOPK_NP * 8192) return MLLM_HIP_ERR_SHAPE;
+    if (n <= TOPK_ONE_WG) {
+        hipLaunchKernelGGL(topk_slice_kernel<1024>, dim3(1, rows), dim3(1024), (size_t)n * 4, st, x, (const int *)nullptr, ld, n, n, k, out_val, out_idx, (int64_t)ldo);
+        return MH_LAUNCH_OK("topk_rows_one");
+    }
+    const int per = (n + TOPK_NP - 1) / TOPK_NP;
+    const int64_t ldc = (int64_t)TOPK_NP * k;
+    float *cv = (float *)scr;
+    int *ci = (int *)(cv + (size_t)rows * ldc);
+    hipLaunchKernelGGL(topk_slice_kernel<256>, dim3(TOPK_NP, rows), dim3(256), (size_t)per * 4, st, x, (const int *)nullptr, ld, n, per, k, cv, ci, ldc);
+    if (int rc = MH_LAUNCH_OK("topk_rows_slices")) return rc;
+    hipLaunchKernelGGL(topk_slice_kernel<1024>, dim3(1, rows), dim3(1024), (size_t)ldc * 4, st, (const float *)cv, (const int *)ci, ldc, (int)ldc, (int)ldc, k, out_val, out_idx,
+                       (int64_t)ldo);
+    return MH_LAUNCH_OK("topk_rows_final");
+}
 }  // namespace mllm_hip
 extern "C" int mllm_hip_topk(const float *x, int n, int k, float *out_val, int *out_idx, void *stream) {
     if (n <= 0 || k <= 0 || k > 64 || k > n) return MLLM_HIP_ERR_SHAPE;
@@ -1194,10 +1233,11 @@ extern "C" int mllm_hip_topk(const float *x, int n, int k, float *out_val, int *
     float *cv = (float *)scr;
     int *ci = (int *)(cv + (size_t)NP * k);
     if (per > 8192) { (void)hipFreeAsync(scr, st); hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), 0, st, x, n, k, out_val, out_idx); return MH_LAUNCH_OK("topk"); }      // rows beyond a million values
-    hipLaunchKernelGGL(topk_slice_kernel<256>, dim3(NP), dim3(256), (size_t)per * 4, st, x, (const int *)nullptr, n, per, k, cv, ci);
+    hipLaunchKernelGGL(topk_slice_kernel<256>, dim3(NP), dim3(256), (size_t)per * 4, st, x, (const int *)nullptr, (int64_t)0, n, per, k, cv, ci, (int64_t)0);
     int rc = MH_LAUNCH_OK("topk_slices");
     if (!rc) {
-        hipLaunchKernelGGL(topk_slice_kernel<1024>, dim3(1), dim3(1024), (size_t)NP * k * 4, st, (const float *)cv, (const int *)ci, NP * k, NP * k, k, out_val, out_idx);
+        hipLaunchKernelGGL(topk_slice_kernel<1024>, dim3(1), dim3(1024), (size_t)NP * k * 4, st, (const float *)cv, (const int *)ci, (int64_t)0, NP * k, NP * k, k, out_val, out_idx,
+                           (int64_t)0);
         rc = MH_LAUNCH_OK("topk_final");
     }
     const hipError_t e = hipFreeAsync(scr, st);

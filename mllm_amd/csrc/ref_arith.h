@@ -65,6 +65,29 @@ __device__ __forceinline__ void fold_first_max(const float *sv, const int *si, f
     for (int w = 1; w < NW; ++w) first_max_merge(best, besti, sv[w], si[w]);
 }
 
+// ---- N2: the temperature softmax over the candidates of the sampling methods (Generate.cpp:69-87 / :120-136; mllm_hip_topk_probs_host is the host form): every
+// step is a double operation on a float promoted to double, rounded once.  The two sums between the steps are sequential and stay with the kernel. ----
+__device__ __forceinline__ double cand_exp_arg(float v, double max_logit, float temperature) { return __ddiv_rn(__dsub_rn((double)v, max_logit), (double)temperature); }
+__device__ __forceinline__ float cand_over_sum(float e, double sum_exp) { return (float)__ddiv_rn((double)e, sum_exp); }      // probs[i] /= sum_exp (a double)
+__device__ __forceinline__ float cand_renorm(float p, float fsum) { return __fdiv_rn(p, fsum); }                              // probs[i] /= _sum (a float)
+// The reference rounds exp()'s double to float.  Its libm exp and the device library's are both within 1 ulp of the true value, so they are within 2 double ulps of each
+// other: unless the device's double lies that close to a float rounding tie, both round to the same float.  true = this value could round either way.
+__device__ __forceinline__ bool f32_rounding_ambiguous(double d) {
+    const uint64_t bits = (uint64_t)__double_as_longlong(d);
+    const int be = (int)((bits >> 52) & 0x7ff);
+    if (be == 0 || be == 0x7ff) return false;      // zero (a double subnormal is a float zero for every neighbour too), infinity, NaN
+    const int e = be - 1023;
+    const int drop = e >= -126 ? 29 : 29 + (-126 - e);      // significand bits the float does not keep (more of them below the float's normal range)
+    if (drop > 54) return false;                              // below 2^-151: zero, whatever the last bits are
+    const uint64_t sig = (bits & 0xfffffffffffffull) | (1ull << 52);
+    const uint64_t low = sig & ((1ull << drop) - 1), half = 1ull << (drop - 1);
+    return (low > half ? low - half : half - low) <= 2;
+}
+// ---- the inverse-CDF step of the draw (mllm_hip_sample_index_host): acc += probs[i] / sum, both double.  The quotients are independent of each other, so a kernel
+// computes them a lane each (cdf_term) and only adds in sequence (cdf_add) ----
+__device__ __forceinline__ double cdf_term(float p, double sum) { return __ddiv_rn((double)p, sum); }
+__device__ __forceinline__ double cdf_add(double acc, double term) { return __dadd_rn(acc, term); }
+
 // ---- A9 RMSNorm after the sum of squares (op/CPURMSNorm.cpp:31-136): the sum is a double, its mean is rounded to fp32 before eps is added ----
 __device__ __forceinline__ float rms_inv(double ss, int dim, float eps) {
     const float m = (float)(ss / (double)dim);

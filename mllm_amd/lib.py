@@ -72,6 +72,7 @@ def load() -> C.CDLL:
         _lib.mllm_hip_model_destroy.restype = None
         _lib.mllm_hip_model_destroy.argtypes = [C.c_void_p]
         _lib.mllm_hip_sort_desc_workspace_bytes.restype = C.c_size_t
+        _lib.mllm_hip_sample_rows_workspace_bytes.restype = C.c_size_t
     return _lib
 
 
@@ -261,6 +262,25 @@ class Model:
         ms = C.c_float()
         check(load().mllm_hip_model_batch_generate(self._h, C.c_int(B), vp(t), C.c_int(int(steps)), C.c_int32(int(eos)), vp(toks), vp(n), C.byref(ms)), "batch_generate")
         return toks, n, ms.value
+
+    def batch_generate_sampled(self, first_tokens, steps, method, u01, top_k=5, top_p=0.92, temperature=0.7, eos=-1):
+        """batch_generate with Module::generate's methods (0 greedy, 1 top-k, 2 top-p; LlmTextGeneratorOpts' defaults), candidates, softmax and draw on the device inside the
+        captured step: (ids int32 [B][steps], n_out int32 [B], n_ambiguous, device ms).  u01: [B][steps] uniform numbers in [0, 1), row b's s-th step draws on u01[b][s]
+        (None only for method 0).  Row b equals generate_sampled of sequence b alone on u01[b] when n_ambiguous == 0 (mllm_hip.h)."""
+        t = np.ascontiguousarray(first_tokens, dtype=np.int32)
+        B, steps = int(t.size), int(steps)
+        u = None
+        if u01 is not None:
+            u = np.ascontiguousarray(u01, dtype=np.float32)
+            if u.size != B * max(steps, 0):
+                raise ValueError("u01 must hold [B][steps] numbers")
+        toks = np.empty((B, max(steps, 0)), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        amb, ms = C.c_int32(), C.c_float()
+        check(load().mllm_hip_model_batch_generate_sampled(self._h, C.c_int(B), vp(t), C.c_int(steps), C.c_int(int(method)), C.c_int(int(top_k)), C.c_float(top_p),
+                                                           C.c_float(temperature), vp(u), C.c_int32(int(eos)), vp(toks), vp(n), C.byref(amb), C.byref(ms)),
+              "batch_generate_sampled")
+        return toks, n, amb.value, ms.value
 
     def batch_prefill(self, prompts, visual_dev=None, grid_thw=None, n_visual_rows=None, want_logits=True):
         """The prompts of sequences 0 .. len(prompts) - 1 in one pass over the weights (each appended to its own cache): (next greedy ids [B], logits [B][vocab] or None,

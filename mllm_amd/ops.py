@@ -427,6 +427,29 @@ def topk_probs(top_val, temperature):
     return p
 
 
+def sample_rows(x, method, u01, top_k=5, top_p=0.92, temperature=0.7, softmax_first=False, n=None):
+    """mllm_hip_sample_rows: both sampling methods (1 top-k, 2 top-p) for every row of x [rows][ld] on the device (n = the row length, default ld).
+    Returns (drawn ids [rows], candidate indices [rows][..], candidate probabilities [rows][..], candidate counts [rows], n_ambiguous), numpy."""
+    x = _dev(x, torch.float32)
+    rows, ld = x.shape
+    n = ld if n is None else int(n)
+    u = _dev(np.ascontiguousarray(u01, dtype=np.float32).reshape(-1))
+    assert u.numel() == rows
+    ldc = n if method == 2 else max(1, int(top_k))
+    ids = torch.empty(rows, dtype=torch.int32, device="cuda")
+    ci = torch.full((rows, ldc), -1, dtype=torch.int32, device="cuda")
+    cp = torch.zeros((rows, ldc), dtype=torch.float32, device="cuda")
+    cn = torch.zeros(rows, dtype=torch.int32, device="cuda")
+    amb = torch.zeros(1, dtype=torch.int32, device="cuda")
+    so = L.load()
+    wsb = int(so.mllm_hip_sample_rows_workspace_bytes(C.c_int(rows), C.c_int(n), C.c_int(method), C.c_int(top_k)))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device="cuda")
+    check(so.mllm_hip_sample_rows(vp(x), i64(ld), C.c_int(rows), C.c_int(n), C.c_int(method), C.c_int(top_k), C.c_float(top_p), C.c_float(temperature),
+                                  C.c_int(1 if softmax_first else 0), vp(u), vp(ids), vp(ci), vp(cp), i64(ldc), vp(cn), vp(amb), vp(ws), C.c_size_t(wsb), _stream()),
+          "sample_rows")
+    return ids.cpu().numpy(), ci.cpu().numpy(), cp.cpu().numpy(), cn.cpu().numpy(), int(amb.item())
+
+
 # ---- SURVEY N4: the extra ops of the other model families (csrc/kernels_n4.hip); index tensors are fp32 like the reference's ------------------------------
 def sliding_window_mask(x, H, keys, window):
     x = _dev(x, torch.float32)
