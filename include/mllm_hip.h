@@ -288,7 +288,13 @@ int mllm_hip_fa2_decode_step_supported(int T, int Hq, int Hkv, int D);
 int mllm_hip_fa2_batch(const float *Q, int64_t ldq, const void *K, int64_t ldk, const void *V, int64_t ldv, int kv_dtype, float *O,
                        int64_t ldo, int Sq, int Sk, int Hq, int Hkv, int D, int causal, int nbatch, int64_t bq, int64_t bk, int64_t bv,
                        int64_t bo, void *stream);
-/* attention on the engine's KV layout: K fp16 rows `[Sk][Hkv*D]`, V fp16 transposed `[Hkv*D][ldvt]` (mllm_hip_store_f16_t) */
+/* attention on the engine's KV layout: K fp16 rows `[Sk][Hkv*D]`, V fp16 transposed `[Hkv*D][ldvt]` (mllm_hip_store_f16_t).
+ * Precondition on the slab: the kernels fetch whole groups of key columns from every row of Vt, past the Sk keys: columns [0, B) with
+ *     B = Sk rounded up to a multiple of 32  when Sq >= 4 (the prefill kernel's chunks of 32 keys),
+ *     B = Sk rounded up to a multiple of 128 when Sq <  4 (the decode walk's chunks of 128 keys).
+ * So ldvt >= B (and ldvt % 8 == 0) is required, MLLM_HIP_ERR_SHAPE otherwise, and the columns [Sk, B) of every row must hold FINITE values: they are multiplied by a
+ * probability of exactly 0 (Sq >= 4) or dropped (Sq < 4), so any finite value leaves the result unchanged, while an Inf or NaN there turns the row's output into NaN
+ * when Sq >= 4.  The resident engine zero-fills its slab and pitches it at round64(cache rows) + 128 >= B for every Sk it can hold. */
 int mllm_hip_fa2_vt(const float *Q, int64_t ldq, const void *K, int64_t ldk, const void *Vt, int64_t ldvt, float *O, int64_t ldo,
                     int Sq, int Sk, int Hq, int Hkv, int D, int causal, void *stream);
 

@@ -620,9 +620,22 @@ extern "C" int mllm_hip_fa2_batch(const float *Q, int64_t ldq, const void *K, in
 
 // Prefill on the engine's own KV layout: K rows fp16 [Sk][Hkv*D] (ldk), V transposed fp16 [Hkv*D][ldvt] (kernels_decode.hip
 // reads the same slab).  Same arithmetic as mllm_hip_fa2 with kv_dtype fp16.
+//
+// The columns of a slab row that a launch reads, beyond the Sk keys (include/mllm_hip.h states this as the entry's precondition):
+//   Sq >= 4   fa2_prefill_kernel's VT fetch takes columns chunk0 .. chunk0 + FA_KCH - 1 of every row, clamped or not, for every chunk0 < klim; the last row block's klim is
+//             sk_eff (r0 + FA_R >= Sq there, so r0 + FA_R + delta + 4 > Sk), and sk_eff rounds up to the same chunk as Sk (they differ only below 16 keys): columns
+//             [0, Sk rounded up to FA_KCH);
+//   Sq < 4    fa2_decode_fetch_v's VT branch takes whole chunks of FA_VCH keys, ceil(Sk / FA_VCH) of them: columns [0, Sk rounded up to FA_VCH).
+// The values in [Sk, bound) meet p = 0 (prefill) or are replaced by 0 (decode walk), so any finite value there is harmless.  The engine's slab passes for every
+// Sk <= T: vt_ld = round64(T) + 128 >= T + 128 > round128(T) >= round128(Sk); so does ops.flash_attention2_vt's round64(Sk) + 128.
+static int64_t fa2_vt_min_ld(int Sq, int Sk) {
+    const int64_t unit = Sq >= 4 ? FA_KCH : FA_VCH;
+    return ((int64_t)Sk + unit - 1) / unit * unit;
+}
 extern "C" int mllm_hip_fa2_vt(const float *Q, int64_t ldq, const void *K, int64_t ldk, const void *Vt, int64_t ldvt, float *O, int64_t ldo, int Sq, int Sk,
                                int Hq, int Hkv, int D, int causal, void *stream) {
     if (Sq <= 0 || Sk <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || (ldk % 8) || (ldvt % 8)) return MLLM_HIP_ERR_SHAPE;
+    if (ldvt < fa2_vt_min_ld(Sq, Sk)) return MLLM_HIP_ERR_SHAPE;
     hipStream_t st = as_stream(stream);
     switch (D) {
     case 64: return launch_fa2<64, true, true>(Q, ldq, K, ldk, Vt, ldvt, O, ldo, Sq, Sk, Hq, Hkv, causal, nullptr, Sk, st);

@@ -347,6 +347,72 @@ def flash_attention2_batch(q, k, v, Sq, Sk, Hq, Hkv, D, causal):
     return o
 
 
+# Attention operands with a pitch: the engine hands the attention entries the fused q|k|v buffer (pitch (Hq + 2 Hkv) D), slabs whose rows go on behind the Sk keys and a
+# transposed V slab of padded rows.  The `_pitched` entries below build such buffers: every element the op does not own holds `poison` (NaN by default: one read of it turns
+# an output row into NaN), `rows_behind` guard rows follow every operand, and the output is sentinel_out's, returned whole, so stray stores show in its pad columns and rows.
+def pitched_in(x, ld, rows_behind, poison=float("nan")):
+    """`x [rows][n]` (fp32 or fp16) as the leading columns of a `[rows + rows_behind][ld]` device buffer of its type; every other element holds `poison`."""
+    x = _dev(x)
+    rows, n = x.shape
+    assert ld >= n and rows_behind >= 0
+    buf = torch.full((rows + rows_behind, ld), poison, dtype=x.dtype, device="cuda")
+    buf[:rows, :n] = x
+    return buf
+
+
+def _pitched_out(rows, ld, out):
+    if out is None:
+        return sentinel_out(rows, ld)
+    assert tuple(out.shape) == (rows, ld) and out.dtype == torch.float32 and out.is_contiguous()
+    return out
+
+
+def flash_attention2_pitched(q, k, v, Sq, Sk, Hq, Hkv, D, causal, ldq, ldk, ldv, ldo, rows_behind=2, poison=float("nan"), out=None):
+    """mllm_hip_fa2 on pitched operands: q fp32 [Sq][Hq*D] in rows of ldq, k / v fp16 or fp32 [Sk][Hkv*D] in rows of ldk / ldv (pitched_in).  Returns the whole
+    `[Sq + rows_behind][ldo]` output (sentinel_out, or `out`, which stays readable when the call is refused)."""
+    qb = pitched_in(_dev(q, torch.float32), ldq, rows_behind, poison)
+    kb, vb = pitched_in(k, ldk, rows_behind, poison), pitched_in(v, ldv, rows_behind, poison)
+    kv_dt = F16 if kb.dtype == torch.float16 else F32
+    o = _pitched_out(Sq + rows_behind, ldo, out)
+    ws = torch.empty(max(L.load().mllm_hip_fa2_workspace_bytes(C.c_int(Sq), C.c_int(Hq), C.c_int(D), C.c_int(Sk)), 16), dtype=torch.uint8, device="cuda")
+    check(L.load().mllm_hip_fa2(vp(qb), i64(ldq), vp(kb), i64(ldk), vp(vb), i64(ldv), C.c_int(kv_dt), vp(o), i64(ldo), C.c_int(Sq), C.c_int(Sk),
+                                C.c_int(Hq), C.c_int(Hkv), C.c_int(D), C.c_int(int(causal)), None, vp(ws), _stream()), "fa2")
+    return o
+
+
+def flash_attention2_vt_pitched(q, k16, v16, Sq, Sk, Hq, Hkv, D, causal, ldq, ldk, ldvt, ldo, rows_behind=2, poison=float("nan"), vt_pad=0.0, out=None):
+    """mllm_hip_fa2_vt on pitched operands: k16 fp16 [Sk][Hkv*D] in rows of ldk; v16 fp16 [Sk][Hkv*D], stored transposed as `[Hkv*D + rows_behind][ldvt]`: columns
+    Sk .. ldvt - 1 of the slab's rows, which the kernels read by design, hold `vt_pad`, the guard rows behind the slab `poison`.  Returns the whole output."""
+    qb = pitched_in(_dev(q, torch.float32), ldq, rows_behind, poison)
+    kb = pitched_in(_dev(k16, torch.float16), ldk, rows_behind, poison)
+    v16 = _dev(v16, torch.float16)
+    assert ldvt >= Sk and tuple(v16.shape) == (Sk, Hkv * D)
+    vt = torch.full((Hkv * D + rows_behind, ldvt), poison, dtype=torch.float16, device="cuda")
+    vt[:Hkv * D, Sk:] = vt_pad
+    vt[:Hkv * D, :Sk] = v16.t()
+    o = _pitched_out(Sq + rows_behind, ldo, out)
+    check(L.load().mllm_hip_fa2_vt(vp(qb), i64(ldq), vp(kb), i64(ldk), vp(vt), i64(ldvt), vp(o), i64(ldo), C.c_int(Sq), C.c_int(Sk), C.c_int(Hq), C.c_int(Hkv), C.c_int(D),
+                                   C.c_int(int(causal)), _stream()), "fa2_vt")
+    return o
+
+
+def flash_attention2_batch_pitched(q, k, v, Sq, Sk, Hq, Hkv, D, causal, ldq, ldk, ldv, ldo, rows_behind=2, poison=float("nan"), out=None):
+    """mllm_hip_fa2_batch on pitched operands: q fp32 [nb][Sq][Hq*D]; k, v fp16 or fp32 [nb][Sk][Hkv*D].  Every set is a pitched_in buffer of its own, so the set strides
+    exceed a set by `rows_behind` rows of poison.  Returns the whole `[nb][Sq + rows_behind][ldo]` output."""
+    q = _dev(q, torch.float32)
+    k, v = _dev(k), _dev(v)
+    nb = q.shape[0]
+    qb = torch.stack([pitched_in(q[b], ldq, rows_behind, poison) for b in range(nb)])
+    kb = torch.stack([pitched_in(k[b], ldk, rows_behind, poison) for b in range(nb)])
+    vb = torch.stack([pitched_in(v[b], ldv, rows_behind, poison) for b in range(nb)])
+    kv_dt = F16 if kb.dtype == torch.float16 else F32
+    o = _pitched_out(nb * (Sq + rows_behind), ldo, out)
+    check(L.load().mllm_hip_fa2_batch(vp(qb), i64(ldq), vp(kb), i64(ldk), vp(vb), i64(ldv), C.c_int(kv_dt), vp(o), i64(ldo), C.c_int(Sq), C.c_int(Sk), C.c_int(Hq),
+                                      C.c_int(Hkv), C.c_int(D), C.c_int(int(causal)), C.c_int(nb), i64((Sq + rows_behind) * ldq), i64((Sk + rows_behind) * ldk),
+                                      i64((Sk + rows_behind) * ldv), i64((Sq + rows_behind) * ldo), _stream()), "fa2_batch")
+    return o.view(nb, Sq + rows_behind, ldo)
+
+
 def linear_q4k_packed_producers(Wq, x, N, mode="quant", w=None, b=None, eps=1e-6):
     """Prefill path of the resident engine: the producer (quantiser / RMSNorm / LayerNorm) writes the packed activation operand, the
     GEMM consumes it.  Returns y = Linear(producer(x))."""
@@ -382,7 +448,7 @@ def linear_q4k_packed_producers(Wq, x, N, mode="quant", w=None, b=None, eps=1e-6
 def flash_attention2_vt(q, k16, v_f32, Sq, Sk, Hq, Hkv, D, causal):
     """Same attention on the resident engine's KV layout: K fp16 rows, V stored transposed (mllm_hip_store_f16_t) with padded rows."""
     q, k16, v_f32 = _dev(q, torch.float32), _dev(k16, torch.float16), _dev(v_f32, torch.float32)
-    ld = ((Sk + 63) // 64) * 64 + 128
+    ld = ((Sk + 63) // 64) * 64 + 128      # the engine's rule; >= Sk + 128 > Sk rounded up to 128, the most mllm_hip_fa2_vt asks for (include/mllm_hip.h)
     vt = torch.zeros((Hkv * D, ld), dtype=torch.float16, device="cuda")
     check(L.load().mllm_hip_store_f16_t(vp(v_f32), i64(Hkv * D), vp(vt), i64(ld), C.c_int(Sk), C.c_int(Hkv * D), _stream()), "store_f16_t")
     o = torch.empty((Sq, Hq * D), dtype=torch.float32, device="cuda")
