@@ -5,7 +5,7 @@
 //   Qwen2VLModel::Forward  mllm/models/qwen2_vl/modeling_qwen2_vl.hpp:381-404                          -> prefill / forward_llm
 //   QWen2Decoder/Attention/MLP :193-335; QWenDecoder modeling_qwen.hpp:60-101; TinyLLaMABlock modeling_tinyllama.hpp:15-42;
 //   LLaMABlock modeling_llama.hpp:40-80 (all: RMSNorm -> MultiHeadAttention (modeling_transformer.hpp:35-219) -> +x -> RMSNorm -> SiLU MLP -> +x)
-//                                                                                                      -> the layer loop of forward_llm
+//                                                                                                      -> llm_layer, shared by the passes
 //   Qwen2VisionModel       modeling_qwen2_vl.hpp:21-191 (patch embed, VisionBlock x32, PatchMerger)   -> forward_vision (kind QWEN2VL)
 //   LLaVAVisionModel       modeling_llava.hpp:39-98 (CLIP: conv patch embed, cls row, position rows, pre_layrnorm, ViTBlock xN, projector)
 //   ViTModel               modeling_vit.hpp:63-111 (conv patch embed + bias, cls, positions, ViTBlock xN, LayerNorm(cls), classifier) -> forward_vision
@@ -897,11 +897,42 @@ static int ensure_vision_buffers(M *m, const int32_t *meta, int NB = 1) {
     return 0;
 }
 
+// One decoder layer over `rows` rows, x in h and back in h (h2: the stream between the two halves), shared by the three passes (forward_llm, batch_step_body,
+// forward_llm_batch).  attn(li) is the pass's own rotary + cache append + attention of layer li, m->qkv -> m->attn; every other Op is row-wise.
+template <typename Attn>
+static int llm_layer(M *m, const M::Layer &L, int li, int rows, float *h, float *h2, Attn &&attn) {
+    const auto &c = m->c;
+    const int H = c.hidden, I = c.inter;
+    EH(q_rmsnorm(m, h, L.in_norm, m->xq, rows, H, c.rms_eps));
+    EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, rows));
+    EH(attn(li));
+    EH(q_quant(m, m->attn, m->xq, rows, m->HD));
+    EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, rows));                          // tmp = o_proj(attn) + x
+    EH(q_rmsnorm(m, h2, L.post_norm, m->xq, rows, H, c.rms_eps));
+    EH(lin(m, L.gu, m->xq, m->gu, MLLM_HIP_F32, 2 * I, nullptr, rows));
+    EH(q_silu_mul_quant(m, m->gu, m->act, m->xq2, rows, I));
+    return lin(m, L.down, m->xq2, h, MLLM_HIP_F32, H, h2, rows);                  // x = down(...) + tmp
+}
+// The head of the three passes: model.norm over the `rows` rows of x, then logits [rows][vocab] -- tied = Tensor::mm with embed_tokens^T through Q8_0 activations (the
+// normed rows and their Q8_0 planes in the caller's normed / x80_* buffers), else the Linear lm_head through Q8_K
+static int llm_head(M *m, const float *x, int rows, float *normed, int8_t *x80_qs, uint16_t *x80_d, float *logits) {
+    const auto &c = m->c;
+    const int H = c.hidden;
+    if (c.tie_embedding) {
+        EH(mllm_hip_rmsnorm(x, m->final_norm, normed, nullptr, nullptr, nullptr, rows, H, c.final_eps, 0, m->st));
+        EH(mllm_hip_quantize_q80(normed, x80_qs, x80_d, rows, H, m->st));
+        return mllm_hip_linear_q40_q80(m->emb_qs, m->emb_d, nullptr, x80_qs, x80_d, logits, c.vocab, rows, c.vocab, H, m->st);
+    }
+    EH(mllm_hip_rmsnorm(x, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, rows, H, c.final_eps, 0, m->st));
+    return mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, logits, MLLM_HIP_F32, c.vocab, nullptr, rows, c.vocab, H, m->st);
+}
+static int argmax_parts(const M *m, int B) { return std::max(1, std::min(m->max_parts / B, 128)); }      // partial maxima per row of the B-row argmax launches
+
 // One LLM forward over S new tokens whose embeddings are in m->h0 ([S][H]); logits of the last token -> m->logits.
 // pos3: QWEN2VL position ids [3][S]; the HF-rotary archs take positions cache_len .. cache_len + S - 1 (CPURoPE's h_cnt_, CPURoPE.cpp:510-513)
 static int forward_llm(M *m, int S, const float *pos3) {
     const auto &c = m->c;
-    const int H = c.hidden, I = c.inter, D = m->D, T0 = m->cache_len, half = D / 2;
+    const int D = m->D, T0 = m->cache_len, half = D / 2;
     hipStream_t st = m->st;
     if (T0 + S > c.cache_limit) { fprintf(stderr, "mllm_hip: KV cache overflow (%d + %d > %d)\n", T0, S, c.cache_limit); return MLLM_HIP_ERR_SHAPE; }
     if (m->mrope) {   // M-RoPE tables for these S positions
@@ -918,32 +949,15 @@ static int forward_llm(M *m, int S, const float *pos3) {
         HH(hipMemcpyAsync(m->rope_sin, m->hf_sin.data() + (size_t)T0 * half, (size_t)S * half * 4, hipMemcpyHostToDevice, st));
         HH(hipMemcpyAsync(m->rope_cos, m->hf_cos.data() + (size_t)T0 * half, (size_t)S * half * 4, hipMemcpyHostToDevice, st));
     }
-    float *h = m->h0, *h2 = m->h1;
-    for (int li = 0; li < c.layers; ++li) {
-        auto &L = m->layers[li];
+    auto attn = [&](int li) -> int {
         uint16_t *kl = m->kslab + (size_t)li * c.cache_limit * m->KVD, *vl = m->vslab + (size_t)li * m->KVD * m->vt_ld;
-        EH(q_rmsnorm(m, h, L.in_norm, m->xq, S, H, c.rms_eps));
-        EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, S));
         // q_rope in place; k_rope -> fp16 slab rows [T0, T0+S); v -> fp16 slab (KVCache zero-copy append)
         EH(mllm_hip_qkv_rope_append(m->qkv, m->QKV, m->rope_sin, m->rope_cos, half, kl + (size_t)T0 * m->KVD, m->KVD, vl + T0, m->vt_ld, S, c.heads, c.kv_heads, D, st));
-        EH(mllm_hip_fa2_vt(m->qkv, m->QKV, kl, m->KVD, vl, m->vt_ld, m->attn, m->HD, S, T0 + S, c.heads, c.kv_heads, D, 1, st));
-        EH(q_quant(m, m->attn, m->xq, S, m->HD));
-        EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, S));                          // tmp = o_proj(attn) + x
-        EH(q_rmsnorm(m, h2, L.post_norm, m->xq, S, H, c.rms_eps));
-        EH(lin(m, L.gu, m->xq, m->gu, MLLM_HIP_F32, 2 * I, nullptr, S));
-        EH(q_silu_mul_quant(m, m->gu, m->act, m->xq2, S, I));
-        EH(lin(m, L.down, m->xq2, h, MLLM_HIP_F32, H, h2, S));                      // x = down(...) + tmp
-    }
-    // final norm on the last token only (norm then clip({-1}) == clip then norm; TinyLLaMAModel does not clip (modeling_tinyllama.hpp:67-75) but the demo
-    // reads the last row), then the head: tied = Tensor::mm with embed_tokens^T through Q8_0 activations, else the Linear lm_head through Q8_K
-    if (c.tie_embedding) {
-        EH(mllm_hip_rmsnorm(h + (size_t)(S - 1) * H, m->final_norm, m->normed, nullptr, nullptr, nullptr, 1, H, c.final_eps, 0, st));
-        EH(mllm_hip_quantize_q80(m->normed, m->x80_qs, m->x80_d, 1, H, st));
-        EH(mllm_hip_linear_q40_q80(m->emb_qs, m->emb_d, nullptr, m->x80_qs, m->x80_d, m->logits, c.vocab, 1, c.vocab, H, st));
-    } else {
-        EH(mllm_hip_rmsnorm(h + (size_t)(S - 1) * H, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, 1, H, c.final_eps, 0, st));
-        EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->logits, MLLM_HIP_F32, c.vocab, nullptr, 1, c.vocab, H, st));
-    }
+        return mllm_hip_fa2_vt(m->qkv, m->QKV, kl, m->KVD, vl, m->vt_ld, m->attn, m->HD, S, T0 + S, c.heads, c.kv_heads, D, 1, st);
+    };
+    for (int li = 0; li < c.layers; ++li) EH(llm_layer(m, m->layers[li], li, S, m->h0, m->h1, attn));
+    // the head on the last token only (norm then clip({-1}) == clip then norm; TinyLLaMAModel does not clip (modeling_tinyllama.hpp:67-75) but the demo reads the last row)
+    EH(llm_head(m, m->h0 + (size_t)(S - 1) * c.hidden, 1, m->normed, m->x80_qs, m->x80_d, m->logits));
     EH(argmax_row_launch(m->dctx, m->logits, c.vocab, m->tok_dev, st));
     m->cache_len = T0 + S;
     return 0;
@@ -951,21 +965,25 @@ static int forward_llm(M *m, int S, const float *pos3) {
 
 static int arm_decode(M *m);
 
+// The synchronisation that ends a call, the merged launches' time-out flag read behind the call's other copies.  A set flag -- a polled hand-off inside a merged launch
+// gave up: the results of the step(s) are not valid -- is cleared and reported as `fmt` (which may name the role that waited with one %s)
+static int sync_check_merged(M *m, const char *fmt) {
+    if (m->plan.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, m->st));
+    HH(hipStreamSynchronize(m->st));
+    if (!m->plan.merge_o || !*m->pin_err) return 0;
+    const int site = *m->pin_err;
+    *m->pin_err = 0;
+    HH(hipMemset(m->poll_err, 0, 4));
+    static const char *const who[] = {"?", "q|k|v role waiting for the layer input row", "o-projection role waiting for the attention's row", "attention role waiting for q|k|v"};
+    set_error_msg(fmt, who[site >= 1 && site <= 3 ? site : 0]);
+    return MLLM_HIP_ERR_ARG;
+}
 static int finish(M *m, float *logits_host, int32_t *next_token, float *elapsed_ms) {
     HH(hipEventRecord(m->ev1, m->st));
     // the copies ride the stream behind the step and ONE synchronisation covers the step and both of them
     if (logits_host) HH(hipMemcpyAsync(logits_host, m->logits, (size_t)m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     if (next_token) HH(hipMemcpyAsync(m->pin_tok + 1, m->tok_dev, 4, hipMemcpyDeviceToHost, m->st));
-    if (m->plan.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, m->st));
-    HH(hipStreamSynchronize(m->st));
-    if (m->plan.merge_o && *m->pin_err) {      // a polled hand-off inside a merged launch gave up: the results of the step(s) are not valid
-        const int site = *m->pin_err;
-        *m->pin_err = 0;
-        HH(hipMemset(m->poll_err, 0, 4));
-        static const char *const who[] = {"?", "q|k|v role waiting for the layer input row", "o-projection role waiting for the attention's row", "attention role waiting for q|k|v"};
-        set_error_msg("a merged decode launch timed out waiting for its producer workgroups (option merge_o): %s", who[site >= 1 && site <= 3 ? site : 0]);
-        return MLLM_HIP_ERR_ARG;
-    }
+    EH(sync_check_merged(m, "a merged decode launch timed out waiting for its producer workgroups (option merge_o): %s"));
     if (next_token) *next_token = m->pin_tok[1];
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
     return 0;
@@ -1188,6 +1206,10 @@ static void seq_park(M *m) {
     auto &q = m->seqs[m->cur_seq];
     q.kslab = m->kslab; q.vslab = m->vslab; q.cache_len = m->cache_len; q.last_pos = m->last_pos;
 }
+// a batched call has moved seqs[0 .. B-1] on: the model's own counters follow the selected sequence, whose fused decode step is re-armed before its next use
+static void seq_sync_selected(M *m, int B) {
+    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+}
 static int seq_select(M *m, int s) {
     seq_park(m);
     if (s == m->cur_seq) return 0;
@@ -1298,37 +1320,21 @@ inline int tail_key(const SampledTail *t) { return t ? (t->method << 8 | t->top_
 }  // namespace
 static int batch_step_body(M *m, int B, const SampledTail *tail = nullptr) {
     const auto &c = m->c;
-    const int H = c.hidden, I = c.inter, D = m->D, half = D / 2;
+    const int D = m->D, half = D / 2;
     hipStream_t st = m->st;
     // from four rows on the Linears take the packed MFMA GEMM: its 32-row tile costs the same for 1 .. 32 rows, the M < 16 GEMV form pays its chain tables per row
     struct MinRows { M *m; int keep; ~MinRows() { m->gemm_min_rows = keep; } } restore{m, m->gemm_min_rows};
     if (B >= 4) m->gemm_min_rows = B;
-    EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, B, H, c.vocab, st));
-    float *h = m->h0, *h2 = m->h1;
-    for (int li = 0; li < c.layers; ++li) {
-        auto &L = m->layers[li];
-        EH(q_rmsnorm(m, h, L.in_norm, m->xq, B, H, c.rms_eps));
-        EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, B));
-        // attention is the one Op that is not row-wise: sequence b's new key / value go to ITS slabs at ITS position, its query walks ITS cache -- all B in one launch each
+    EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, B, c.hidden, c.vocab, st));
+    // attention is the one Op that is not row-wise: sequence b's new key / value go to ITS slabs at ITS position, its query walks ITS cache -- all B in one launch each
+    auto attn = [&](int li) -> int {
         const int64_t koff = (int64_t)li * c.cache_limit * m->KVD, voff = (int64_t)li * m->KVD * m->vt_ld;
         EH(seqs_rope_append_launch(m->qkv, m->QKV, m->btab_sin, m->btab_cos, half, c.cache_limit, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, B, c.heads, c.kv_heads, D,
                                    c.cache_limit, st));
-        EH(seqs_fa2_decode_launch(m->qkv, m->QKV, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, B, c.heads, c.kv_heads, D, c.cache_limit, st));
-        EH(q_quant(m, m->attn, m->xq, B, m->HD));
-        EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, B));
-        EH(q_rmsnorm(m, h2, L.post_norm, m->xq, B, H, c.rms_eps));
-        EH(lin(m, L.gu, m->xq, m->gu, MLLM_HIP_F32, 2 * I, nullptr, B));
-        EH(q_silu_mul_quant(m, m->gu, m->act, m->xq2, B, I));
-        EH(lin(m, L.down, m->xq2, h, MLLM_HIP_F32, H, h2, B));
-    }
-    if (c.tie_embedding) {
-        EH(mllm_hip_rmsnorm(h, m->final_norm, m->bnormed, nullptr, nullptr, nullptr, B, H, c.final_eps, 0, st));
-        EH(mllm_hip_quantize_q80(m->bnormed, m->bx80_qs, m->bx80_d, B, H, st));
-        EH(mllm_hip_linear_q40_q80(m->emb_qs, m->emb_d, nullptr, m->bx80_qs, m->bx80_d, m->blogits, c.vocab, B, c.vocab, H, st));
-    } else {
-        EH(mllm_hip_rmsnorm(h, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, B, H, c.final_eps, 0, st));
-        EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->blogits, MLLM_HIP_F32, c.vocab, nullptr, B, c.vocab, H, st));
-    }
+        return seqs_fa2_decode_launch(m->qkv, m->QKV, m->seqkv_dev, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, B, c.heads, c.kv_heads, D, c.cache_limit, st);
+    };
+    for (int li = 0; li < c.layers; ++li) EH(llm_layer(m, m->layers[li], li, B, m->h0, m->h1, attn));
+    EH(llm_head(m, m->h0, B, m->bnormed, m->bx80_qs, m->bx80_d, m->blogits));
     if (tail) {
         SampleRows a{};
         a.x = m->blogits; a.ld = c.vocab; a.rows = B; a.n = c.vocab; a.method = tail->method; a.top_k = tail->top_k;
@@ -1338,8 +1344,7 @@ static int batch_step_body(M *m, int B, const SampledTail *tail = nullptr) {
         EH(sample_rows_launch(a, st));
         return seqs_sample_next_launch(m->bs_drawn, B, c.cache_limit, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
     }
-    const int np = std::max(1, std::min(m->max_parts / B, 128));
-    return seqs_argmax_next_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
+    return seqs_argmax_next_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, argmax_parts(m, B), m->seqkv_dev, m->bctl, m->btok, m->ids_f, m->bhist, c.cache_limit, st);
 }
 // the batched entry points' page-locked staging block (grown on demand; nothing of it is in flight between calls: every call ends with a synchronisation)
 static int ensure_batch_pin(M *m, size_t need_b) {
@@ -1351,6 +1356,8 @@ static int ensure_batch_pin(M *m, size_t need_b) {
     }
     return 0;
 }
+// the block's layout: a call's regions one after the other, each on a 64-byte boundary; `end` is the size the block needs
+struct PinLayout { size_t end = 0; size_t take(size_t n) { const size_t at = (end + 63) & ~(size_t)63; end = at + n; return at; } };
 extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32_t *tokens, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
     if (!m || !m->has_llm || !tokens || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
     EH(batch_check(m, B, 1, "mllm_hip_model_batch_decode"));
@@ -1372,7 +1379,7 @@ extern "C" int mllm_hip_model_batch_decode(mllm_hip_model *m, int B, const int32
     if (next_tokens) memcpy(next_tokens, m->pf_pin + lg_bytes, (size_t)B * 4);
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
     for (int b = 0; b < B; ++b) { m->seqs[b].cache_len += 1; m->seqs[b].last_pos += 1.0f; }
-    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+    seq_sync_selected(m, B);
     return MLLM_HIP_OK;
 }
 
@@ -1411,7 +1418,7 @@ static int batch_read_state(M *m, int B, std::vector<SeqKV> &desc) {
         m->seqs[b].cache_len = desc[b].t;
         m->seqs[b].last_pos += (float)grew;
     }
-    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+    seq_sync_selected(m, B);
     return 0;
 }
 // the loop of both batch_generate entry points: state uploaded -> `steps` steps (fewer once every row has stopped) -> the host's counters re-read from the device state
@@ -1450,6 +1457,14 @@ extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int
     }
     return MLLM_HIP_OK;
 }
+// Module::generate's method switch (0 greedy, 1 top-k, 2 top-p) as both sampled entry points take it: what they refuse, and when a method is the first-maximum argmax
+static int sampling_check(const M *m, int method, int top_k, float top_p, float temperature, const float *u01) {
+    if (method < 0 || method > 2 || (method != 0 && (!u01 || !(temperature > 0.0f)))) return MLLM_HIP_ERR_ARG;
+    if (method == 1 && (top_k < 0 || top_k > 64 || top_k > m->c.vocab)) return MLLM_HIP_ERR_SHAPE;
+    if (method == 2 && !(top_p > 0.0f)) return MLLM_HIP_ERR_ARG;      // p <= 0 or NaN keeps no candidate at all (the reference then indexes an empty vector, Generate.cpp:116-118)
+    return 0;
+}
+static bool sampling_is_argmax(int method, int top_k) { return method == 0 || (method == 1 && top_k <= 1); }      // greedy, and top-k with k in {0, 1} (Generate.cpp:50-54)
 // batch_generate with Module::generate's method switch (mllm/Generate.cpp:45-142): method 0 is batch_generate's step unchanged; methods 1 and 2 end the step in the
 // sampled tail (batch_step_body), so the candidates, the temperature softmax over them (Generate.cpp:69-87 / :120-136), the draw (Generate.hpp:38-44, as an inverse
 // CDF on u01[b][step of row b]) and the state advance all stay on the device: nothing crosses PCIe between steps.  What a call changes without a new graph -- top_p,
@@ -1457,18 +1472,15 @@ extern "C" int mllm_hip_model_batch_generate(mllm_hip_model *m, int B, const int
 // Uploads and read-backs are staged in the page-locked block (ensure_batch_pin), never on the caller's pageable arrays.
 extern "C" int mllm_hip_model_batch_generate_sampled(mllm_hip_model *m, int B, const int32_t *first_tokens, int steps, int method, int top_k, float top_p, float temperature,
                                                      const float *u01, int32_t eos, int32_t *tokens_host, int32_t *n_out, int32_t *n_ambiguous, float *elapsed_ms) {
-    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0 || method < 0 || method > 2) return MLLM_HIP_ERR_ARG;
-    if (method != 0 && (!u01 || !(temperature > 0.0f))) return MLLM_HIP_ERR_ARG;
-    if (method == 1 && (top_k < 0 || top_k > 64 || top_k > m->c.vocab)) return MLLM_HIP_ERR_SHAPE;
-    if (method == 2 && !(top_p > 0.0f)) return MLLM_HIP_ERR_ARG;      // p <= 0 or NaN keeps no candidate at all (generate_sampled's rule)
+    if (!m || !m->has_llm || !first_tokens || B < 1 || B > m->batch_cap || steps <= 0) return MLLM_HIP_ERR_ARG;
+    EH(sampling_check(m, method, top_k, top_p, temperature, u01));
     EH(batch_check(m, B, steps, "mllm_hip_model_batch_generate_sampled"));
     const auto &c = m->c;
-    // greedy, and top-k with k in {0, 1} (Generate.cpp:50-54), are the first-maximum argmax: batch_generate's tail
-    const bool sampled = method == 2 || (method == 1 && top_k > 1);
+    const bool sampled = !sampling_is_argmax(method, top_k);      // the argmax: batch_generate's tail
     const SampledTail tail = {method, method == 1 ? top_k : 0};
-    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t n_u = (size_t)B * steps, o_ctl = up64(n_u * 4), o_hist = o_ctl + up64(sizeof(SampleCtl));
-    EH(ensure_batch_pin(m, o_hist + n_u * 4));
+    PinLayout pin;      // the uniform numbers (up), the control words (up and back), the ids (back)
+    const size_t n_u = (size_t)B * steps, o_u01 = pin.take(n_u * 4), o_ctl = pin.take(sizeof(SampleCtl)), o_hist = pin.take(n_u * 4);
+    EH(ensure_batch_pin(m, pin.end));
     if (sampled) {
         // the tail's device memory; whatever is replaced here is an address the live graph holds
         const size_t ws_b = sample_rows_workspace_bytes(m->batch_cap, c.vocab, method, method == 1 ? 64 : 0);
@@ -1488,10 +1500,10 @@ extern "C" int mllm_hip_model_batch_generate_sampled(mllm_hip_model *m, int B, c
         }
         if (!m->bs_ctl) EH(m->dalloc(&m->bs_ctl, sizeof(SampleCtl)));
         if (m->bs_drawn_cap < m->batch_cap) { EH(drop_batch_graph(m)); EH(m->dalloc(&m->bs_drawn, (size_t)m->batch_cap * 4)); m->bs_drawn_cap = m->batch_cap; }
-        memcpy(m->pf_pin, u01, n_u * 4);
+        memcpy(m->pf_pin + o_u01, u01, n_u * 4);
         const SampleCtl ctl = {top_p, temperature, steps, 0};
         memcpy(m->pf_pin + o_ctl, &ctl, sizeof(ctl));
-        HH(hipMemcpyAsync(m->bs_u01, m->pf_pin, n_u * 4, hipMemcpyHostToDevice, m->st));
+        HH(hipMemcpyAsync(m->bs_u01, m->pf_pin + o_u01, n_u * 4, hipMemcpyHostToDevice, m->st));
         HH(hipMemcpyAsync(m->bs_ctl, m->pf_pin + o_ctl, sizeof(ctl), hipMemcpyHostToDevice, m->st));
     }
     EH(batch_upload_state(m, B, first_tokens, eos));      // synchronises: the inputs are resident when the clock starts
@@ -1511,11 +1523,11 @@ extern "C" int mllm_hip_model_batch_generate_sampled(mllm_hip_model *m, int B, c
 }
 
 // ---- batched prefill: the prompts of sequences 0 .. B-1 in ONE pass over the weights ---------------------------------------------------------------------------------
-// The R = sum of S_b prompt rows sit concatenated, sequence after sequence, in the activation buffers and run through forward_llm's per-layer Ops once: everything
+// The R = sum of S_b prompt rows sit concatenated, sequence after sequence, in the activation buffers and run through the layers (llm_layer) once: everything
 // row-wise (norms, quantisers, Linears -- the packed GEMM from 16 rows, the GEMV below, as lin() chooses -- SiLU, residual adds) over all R rows, the two Ops that see a
 // sequence -- rotary + cache append, causal attention -- in their variable-length forms, which read a per-sequence descriptor from device memory (decode_launch.h
 // PrefillSeq).  A sequence with fewer than four rows takes the reference's Br = Bc = 1 recurrence, as launch_fa2 does for Sq < 4: its rows go through the decode walk
-// (PrefillRow), never through the 32-row kernel.  The head runs over the B last rows, gathered, with the B-row calls of batch_step_body.  Sequence b's results are, bit
+// (PrefillRow), never through the 32-row kernel.  The head (llm_head) runs over the B last rows, gathered, as in batch_step_body.  Sequence b's results are, bit
 // for bit, those of batch_select(b) + mllm_hip_model_prefill alone (tests/test_batch_prefill.py).
 namespace {
 struct PrefillPlan {
@@ -1523,46 +1535,37 @@ struct PrefillPlan {
     std::vector<PrefillSeq> desc;
     std::vector<PrefillRow> rows;
     std::vector<int> last, where;
-    std::vector<float> last_pos;
+    std::vector<float> last_pos, pos3;      // every sequence's rotary position after the call; M-RoPE: the position ids [3][R] of the R rows
+    PinLayout pin; size_t o_sin, o_cos, o_ids, o_desc, o_last, o_rows, o_where, o_tok, o_logits;      // the call's regions in the page-locked block
 };
 }  // namespace
-// embeddings of the R rows in m->h0, rotary tables in m->rope_sin / rope_cos, descriptors uploaded -> logits of every sequence's last row in m->blogits, ids in m->btok
-static int forward_llm_batch(M *m, int B, const PrefillPlan &pp) {
+// The timed pass: ids of the R rows in m->ids_f, rotary tables in m->rope_sin / rope_cos, descriptors uploaded -> every sequence's last-row logits in m->blogits, ids in m->btok
+static int forward_llm_batch(M *m, int B, const PrefillPlan &pp, const float *visual_dev) {
     const auto &c = m->c;
-    const int H = c.hidden, I = c.inter, D = m->D, half = D / 2, R = pp.R;
+    const int D = m->D, half = D / 2;
     hipStream_t st = m->st;
-    float *h = m->h0, *h2 = m->h1;
-    for (int li = 0; li < c.layers; ++li) {
-        auto &L = m->layers[li];
+    HH(hipEventRecord(m->ev0, st));
+    EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, pp.R, c.hidden, c.vocab, st));
+    // row i of the image prompts' tower output goes to the i-th image token of the concatenated prompts (where + index_put, modeling_qwen2_vl.hpp:386-393)
+    if (pp.n_vis) EH(mllm_hip_index_put_rows(m->h0, visual_dev, m->idx_i, pp.n_vis, c.hidden, st));
+    auto attn = [&](int li) -> int {
         const int64_t koff = (int64_t)li * c.cache_limit * m->KVD, voff = (int64_t)li * m->KVD * m->vt_ld;
-        EH(q_rmsnorm(m, h, L.in_norm, m->xq, R, H, c.rms_eps));
-        EH(lin(m, L.qkv, m->xq, m->qkv, MLLM_HIP_F32, m->QKV, nullptr, R));
         EH(prefill_seqs_rope_append_launch(m->qkv, m->QKV, m->rope_sin, m->rope_cos, half, m->pf_seqs, koff, voff, m->KVD, m->vt_ld, B, pp.max_S, c.heads, c.kv_heads, D, st));
         EH(prefill_seqs_fa2_launch(m->qkv, m->QKV, m->pf_seqs, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, B, pp.max_S, c.heads, c.kv_heads, D, st));
-        EH(prefill_rows_fa2_decode_launch(m->qkv, m->QKV, m->pf_rows, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, pp.n_short, c.heads, c.kv_heads, D, c.cache_limit, st));
-        EH(q_quant(m, m->attn, m->xq, R, m->HD));
-        EH(lin(m, L.o, m->xq, h2, MLLM_HIP_F32, H, h, R));
-        EH(q_rmsnorm(m, h2, L.post_norm, m->xq, R, H, c.rms_eps));
-        EH(lin(m, L.gu, m->xq, m->gu, MLLM_HIP_F32, 2 * I, nullptr, R));
-        EH(q_silu_mul_quant(m, m->gu, m->act, m->xq2, R, I));
-        EH(lin(m, L.down, m->xq2, h, MLLM_HIP_F32, H, h2, R));
-    }
-    // the last row of every sequence, gathered into B contiguous rows (h2 is free after the last layer), then the final norm and the head over the B rows
-    EH(gather_rows_launch(h, m->pf_last, h2, B, H, st));
-    if (c.tie_embedding) {
-        EH(mllm_hip_rmsnorm(h2, m->final_norm, m->bnormed, nullptr, nullptr, nullptr, B, H, c.final_eps, 0, st));
-        EH(mllm_hip_quantize_q80(m->bnormed, m->bx80_qs, m->bx80_d, B, H, st));
-        EH(mllm_hip_linear_q40_q80(m->emb_qs, m->emb_d, nullptr, m->bx80_qs, m->bx80_d, m->blogits, c.vocab, B, c.vocab, H, st));
-    } else {
-        EH(mllm_hip_rmsnorm(h2, m->final_norm, nullptr, m->xq.qs, m->xq.d, m->xq.bs, B, H, c.final_eps, 0, st));
-        EH(mllm_hip_linear_q4k_q8k(m->head.w, nullptr, m->xq.qs, m->xq.d, m->xq.bs, m->blogits, MLLM_HIP_F32, c.vocab, nullptr, B, c.vocab, H, st));
-    }
-    const int np = std::max(1, std::min(m->max_parts / B, 128));
-    return rows_argmax_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, np, m->btok, st);
+        return prefill_rows_fa2_decode_launch(m->qkv, m->QKV, m->pf_rows, koff, voff, m->KVD, m->vt_ld, m->attn, m->HD, pp.n_short, c.heads, c.kv_heads, D, c.cache_limit, st);
+    };
+    for (int li = 0; li < c.layers; ++li) EH(llm_layer(m, m->layers[li], li, pp.R, m->h0, m->h1, attn));
+    // the last row of every sequence, gathered into B contiguous rows (h1 is free after the last layer), then the head over the B rows
+    EH(gather_rows_launch(m->h0, m->pf_last, m->h1, B, c.hidden, st));
+    EH(llm_head(m, m->h1, B, m->bnormed, m->bx80_qs, m->bx80_d, m->blogits));
+    EH(rows_argmax_launch(m->blogits, c.vocab, c.vocab, B, m->part_val, m->part_idx, argmax_parts(m, B), m->btok, st));
+    HH(hipEventRecord(m->ev1, st));
+    return 0;
 }
-extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int32_t *ids, const int32_t *n_ids, const float *visual_dev, const int32_t *image_meta,
-                                            const int32_t *n_visual_rows, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
-    if (!m || !m->has_llm || !ids || !n_ids || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
+// mllm_hip_model_batch_prefill's four jobs, in the order it runs them.  (1) The plan: everything the call refuses and everything the pass needs, from the arguments and the
+// host's counters alone -- no HIP call, no counter moved, so a refused call leaves all state as it was
+static int batch_prefill_plan(M *m, int B, const int32_t *ids, const int32_t *n_ids, const float *visual_dev, const int32_t *image_meta, const int32_t *n_visual_rows,
+                              bool want_logits, PrefillPlan &pp) {
     const auto &c = m->c;
     seq_park(m);
     bool has_vis = false;
@@ -1579,7 +1582,6 @@ extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int3
         int nt, vcols; size_t ie;
         vision_dims(m, image_meta, &nt, &vrows, &vcols, &ie);
     }
-    PrefillPlan pp;
     pp.desc.resize(B); pp.last.resize(B); pp.last_pos.resize(B);
     int64_t total = 0;
     for (int b = 0; b < B; ++b) {
@@ -1591,7 +1593,9 @@ extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int3
         set_error_msg("mllm_hip_model_batch_prefill: %lld prompt rows in one pass, the activation buffers hold cache_limit = %d rows", (long long)total, c.cache_limit);
         return MLLM_HIP_ERR_SHAPE;
     }
-    const int R = (int)total, half = m->D / 2;
+    const int R = (int)total;
+    std::vector<float> pos;
+    if (m->mrope) pp.pos3.resize((size_t)3 * R);
     for (int b = 0, row0 = 0; b < B; row0 += n_ids[b], ++b) {
         const int S = n_ids[b], T0 = m->seqs[b].cache_len, Sk = T0 + S, Tc = Sk / 4;
         pp.desc[b] = PrefillSeq{m->seqs[b].kslab, m->seqs[b].vslab, row0, S, T0, Sk, Tc * 4 + (Tc ? Sk % Tc : 0), 0};      // sk_eff: launch_fa2's expression for fp16 K / V
@@ -1607,76 +1611,73 @@ extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int3
                 return MLLM_HIP_ERR_SHAPE;
             }
         }
-    }
-    pp.R = R; pp.n_short = (int)pp.rows.size(); pp.n_vis = (int)pp.where.size();
-    // rotary rows of the R positions.  HF rotary: row r of sequence b is position T0_b + r (CPURoPE's h_cnt_); M-RoPE: get_rope_index per sequence on its own ids, the
-    // position ids concatenated along the sequence axis and handed to the one table builder
-    // Everything the call uploads, and what it reads back, is staged in ONE page-locked block of the engine's own (pin_tok's rule: no pageable staging).  An asynchronous
-    // copy on pageable memory makes the runtime page-lock the caller's range on the fly and keep that mapping; the engine does not leave such mappings of memory it does
-    // not own behind.
-    const size_t n_tab = (size_t)R * half;
-    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t o_sin = 0, o_cos = o_sin + up64(n_tab * 4), o_ids = o_cos + up64(n_tab * 4), o_desc = o_ids + up64((size_t)R * 4), o_last = o_desc + up64((size_t)B * sizeof(PrefillSeq)),
-                 o_rows = o_last + up64((size_t)B * 4), o_where = o_rows + up64((size_t)pp.n_short * sizeof(PrefillRow)), o_tok = o_where + up64((size_t)pp.n_vis * 4),
-                 o_logits = o_tok + up64((size_t)B * 4), need_b = o_logits + (logits_host ? (size_t)B * c.vocab * 4 : 0);
-    EH(ensure_batch_pin(m, need_b));
-    float *ts = reinterpret_cast<float *>(m->pf_pin + o_sin), *tc = reinterpret_cast<float *>(m->pf_pin + o_cos), *idf = reinterpret_cast<float *>(m->pf_pin + o_ids);
-    // rotary rows of the R positions.  HF rotary: row r of sequence b is position T0_b + r (CPURoPE's h_cnt_); M-RoPE: get_rope_index per sequence on its own ids, the
-    // position ids concatenated along the sequence axis and handed to the one table builder
-    if (m->mrope) {
-        std::vector<float> pos3((size_t)3 * R), pos;
-        for (int b = 0; b < B; ++b) {
-            const int S = n_ids[b], row0 = pp.desc[b].row0;
+        // rotary positions of its rows.  HF rotary: row r is position T0 + r (CPURoPE's h_cnt_); M-RoPE: get_rope_index on the sequence's own ids, the position ids
+        // concatenated along the sequence axis for the one table builder
+        pp.last_pos[b] = (float)(Sk - 1);
+        if (m->mrope) {
             rope_index(m, ids + row0, S, image_meta, has_vis && n_visual_rows[b] > 0, pos);
-            for (int a = 0; a < 3; ++a) memcpy(&pos3[(size_t)a * R + row0], &pos[(size_t)a * S], (size_t)S * 4);
+            for (int a = 0; a < 3; ++a) memcpy(&pp.pos3[(size_t)a * R + row0], &pos[(size_t)a * S], (size_t)S * 4);
             pp.last_pos[b] = pos[(size_t)S - 1];
         }
-        EH(mllm_hip_mrope_table(c.rope_theta, m->D, pos3.data(), R, c.mrope_section, 3, ts, tc));
+    }
+    pp.R = R; pp.n_short = (int)pp.rows.size(); pp.n_vis = (int)pp.where.size();
+    const size_t n_tab = (size_t)R * (m->D / 2);
+    pp.o_sin = pp.pin.take(n_tab * 4); pp.o_cos = pp.pin.take(n_tab * 4); pp.o_ids = pp.pin.take((size_t)R * 4); pp.o_desc = pp.pin.take((size_t)B * sizeof(PrefillSeq));
+    pp.o_last = pp.pin.take((size_t)B * 4); pp.o_rows = pp.pin.take((size_t)pp.n_short * sizeof(PrefillRow)); pp.o_where = pp.pin.take((size_t)pp.n_vis * 4);
+    pp.o_tok = pp.pin.take((size_t)B * 4); pp.o_logits = pp.pin.take(want_logits ? (size_t)B * c.vocab * 4 : 0);
+    return 0;
+}
+// (2) Everything the call uploads, and what it reads back, is staged in ONE page-locked block of the engine's own (pin_tok's rule: no pageable staging).  An asynchronous
+// copy on pageable memory makes the runtime page-lock the caller's range on the fly and keep that mapping; the engine does not leave such mappings of memory it does
+// not own behind.  Synchronised: the inputs are resident when the clock starts
+static int batch_prefill_upload(M *m, int B, const int32_t *ids, const PrefillPlan &pp) {
+    const int R = pp.R, half = m->D / 2;
+    const size_t n_tab = (size_t)R * half;
+    EH(ensure_batch_pin(m, pp.pin.end));
+    float *ts = reinterpret_cast<float *>(m->pf_pin + pp.o_sin), *tc = reinterpret_cast<float *>(m->pf_pin + pp.o_cos), *idf = reinterpret_cast<float *>(m->pf_pin + pp.o_ids);
+    if (m->mrope) {
+        EH(mllm_hip_mrope_table(m->c.rope_theta, m->D, pp.pos3.data(), R, m->c.mrope_section, 3, ts, tc));
     } else {
         for (int b = 0; b < B; ++b) {
-            const size_t n = (size_t)n_ids[b] * half, src = (size_t)pp.desc[b].T0 * half, dst = (size_t)pp.desc[b].row0 * half;
+            const size_t n = (size_t)pp.desc[b].S * half, src = (size_t)pp.desc[b].T0 * half, dst = (size_t)pp.desc[b].row0 * half;
             memcpy(ts + dst, &m->hf_sin[src], n * 4); memcpy(tc + dst, &m->hf_cos[src], n * 4);
-            pp.last_pos[b] = (float)(pp.desc[b].Sk - 1);
         }
     }
     for (int i = 0; i < R; ++i) idf[i] = (float)ids[i];
-    memcpy(m->pf_pin + o_desc, pp.desc.data(), (size_t)B * sizeof(PrefillSeq));
-    memcpy(m->pf_pin + o_last, pp.last.data(), (size_t)B * 4);
-    if (pp.n_short) memcpy(m->pf_pin + o_rows, pp.rows.data(), (size_t)pp.n_short * sizeof(PrefillRow));
-    if (pp.n_vis) memcpy(m->pf_pin + o_where, pp.where.data(), (size_t)pp.n_vis * 4);
+    memcpy(m->pf_pin + pp.o_desc, pp.desc.data(), (size_t)B * sizeof(PrefillSeq));
+    memcpy(m->pf_pin + pp.o_last, pp.last.data(), (size_t)B * 4);
+    if (pp.n_short) memcpy(m->pf_pin + pp.o_rows, pp.rows.data(), (size_t)pp.n_short * sizeof(PrefillRow));
+    if (pp.n_vis) memcpy(m->pf_pin + pp.o_where, pp.where.data(), (size_t)pp.n_vis * 4);
     hipStream_t st = m->st;
     HH(hipMemcpyAsync(m->rope_sin, ts, n_tab * 4, hipMemcpyHostToDevice, st));
     HH(hipMemcpyAsync(m->rope_cos, tc, n_tab * 4, hipMemcpyHostToDevice, st));
     HH(hipMemcpyAsync(m->ids_f, idf, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    HH(hipMemcpyAsync(m->pf_seqs, m->pf_pin + o_desc, (size_t)B * sizeof(PrefillSeq), hipMemcpyHostToDevice, st));
-    HH(hipMemcpyAsync(m->pf_last, m->pf_pin + o_last, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (pp.n_short) HH(hipMemcpyAsync(m->pf_rows, m->pf_pin + o_rows, (size_t)pp.n_short * sizeof(PrefillRow), hipMemcpyHostToDevice, st));
-    if (pp.n_vis) HH(hipMemcpyAsync(m->idx_i, m->pf_pin + o_where, (size_t)pp.n_vis * 4, hipMemcpyHostToDevice, st));
-    HH(hipStreamSynchronize(st));      // the inputs are resident when the clock starts
-    HH(hipEventRecord(m->ev0, st));
-    EH(mllm_hip_embedding_q40(m->ids_f, m->emb_qs, m->emb_d, m->h0, R, c.hidden, c.vocab, st));
-    // row i of the image prompts' tower output goes to the i-th image token of the concatenated prompts (where + index_put, modeling_qwen2_vl.hpp:386-393)
-    if (pp.n_vis) EH(mllm_hip_index_put_rows(m->h0, visual_dev, m->idx_i, pp.n_vis, c.hidden, st));
-    EH(forward_llm_batch(m, B, pp));
-    HH(hipEventRecord(m->ev1, st));
-    if (logits_host) HH(hipMemcpyAsync(m->pf_pin + o_logits, m->blogits, (size_t)B * c.vocab * 4, hipMemcpyDeviceToHost, st));
-    if (next_tokens) HH(hipMemcpyAsync(m->pf_pin + o_tok, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    // a decode step before this call may have left the merged launches' time-out flag set: it is reported (and cleared) here as finish() does, not handed on
-    if (m->plan.merge_o) HH(hipMemcpyAsync(m->pin_err, m->poll_err, 4, hipMemcpyDeviceToHost, st));
+    HH(hipMemcpyAsync(m->pf_seqs, m->pf_pin + pp.o_desc, (size_t)B * sizeof(PrefillSeq), hipMemcpyHostToDevice, st));
+    HH(hipMemcpyAsync(m->pf_last, m->pf_pin + pp.o_last, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (pp.n_short) HH(hipMemcpyAsync(m->pf_rows, m->pf_pin + pp.o_rows, (size_t)pp.n_short * sizeof(PrefillRow), hipMemcpyHostToDevice, st));
+    if (pp.n_vis) HH(hipMemcpyAsync(m->idx_i, m->pf_pin + pp.o_where, (size_t)pp.n_vis * 4, hipMemcpyHostToDevice, st));
     HH(hipStreamSynchronize(st));
-    if (m->plan.merge_o && *m->pin_err) {
-        *m->pin_err = 0;
-        HH(hipMemset(m->poll_err, 0, 4));
-        set_error_msg("mllm_hip_model_batch_prefill: a merged decode launch before this call timed out waiting for its producer workgroups (option merge_o)");
-        return MLLM_HIP_ERR_ARG;
-    }
-    if (logits_host) memcpy(logits_host, m->pf_pin + o_logits, (size_t)B * c.vocab * 4);
-    if (next_tokens) memcpy(next_tokens, m->pf_pin + o_tok, (size_t)B * 4);
+    return 0;
+}
+// (3) is forward_llm_batch.  (4), the entry point's own body: the results come back through the block, and the host's counters move only when the whole pass has run --
+// after a failure they still describe the caches as they were (the rows a failed pass appended lie beyond every cache_len)
+extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int32_t *ids, const int32_t *n_ids, const float *visual_dev, const int32_t *image_meta,
+                                            const int32_t *n_visual_rows, float *logits_host, int32_t *next_tokens, float *elapsed_ms) {
+    if (!m || !m->has_llm || !ids || !n_ids || B < 1 || B > m->batch_cap) return MLLM_HIP_ERR_ARG;
+    PrefillPlan pp;
+    EH(batch_prefill_plan(m, B, ids, n_ids, visual_dev, image_meta, n_visual_rows, logits_host != nullptr, pp));      // every refusal comes from here: before the first HIP call
+    EH(batch_prefill_upload(m, B, ids, pp));
+    EH(forward_llm_batch(m, B, pp, visual_dev));
+    const size_t lg_bytes = (size_t)B * m->c.vocab * 4;
+    if (logits_host) HH(hipMemcpyAsync(m->pf_pin + pp.o_logits, m->blogits, lg_bytes, hipMemcpyDeviceToHost, m->st));
+    if (next_tokens) HH(hipMemcpyAsync(m->pf_pin + pp.o_tok, m->btok, (size_t)B * 4, hipMemcpyDeviceToHost, m->st));
+    // a decode step before this call may have left the merged launches' time-out flag set: it is reported (and cleared) here as finish() does, not handed on
+    EH(sync_check_merged(m, "mllm_hip_model_batch_prefill: a merged decode launch before this call timed out waiting for its producer workgroups (option merge_o)"));
+    if (logits_host) memcpy(logits_host, m->pf_pin + pp.o_logits, lg_bytes);
+    if (next_tokens) memcpy(next_tokens, m->pf_pin + pp.o_tok, (size_t)B * 4);
     if (elapsed_ms) HH(hipEventElapsedTime(elapsed_ms, m->ev0, m->ev1));
-    // the host's counters move only now, when the whole pass has run: after a failure above they still describe the caches as they were (the rows a failed pass
-    // appended lie beyond every cache_len)
     for (int b = 0; b < B; ++b) { m->seqs[b].cache_len = pp.desc[b].Sk; m->seqs[b].last_pos = pp.last_pos[b]; }
-    if (m->cur_seq < B) { m->cache_len = m->seqs[m->cur_seq].cache_len; m->last_pos = m->seqs[m->cur_seq].last_pos; m->needs_arm = true; }
+    seq_sync_selected(m, B);
     return MLLM_HIP_OK;
 }
 
@@ -1687,10 +1688,8 @@ extern "C" int mllm_hip_model_batch_prefill(mllm_hip_model *m, int B, const int3
 // the reference seeds a std::discrete_distribution from std::random_device (Generate.hpp:38-44), which no caller can reproduce.
 extern "C" int mllm_hip_model_generate_sampled(mllm_hip_model *m, int32_t first_token, int steps, int method, int top_k, float top_p, float temperature,
                                                const float *u01, int32_t eos, int32_t *tokens_host, int *n_out, float *elapsed_ms) {
-    if (!m || !m->has_llm || m->cache_len <= 0 || steps <= 0 || method < 0 || method > 2) return MLLM_HIP_ERR_ARG;
-    if (method != 0 && (!u01 || !(temperature > 0.0f))) return MLLM_HIP_ERR_ARG;
-    if (method == 1 && (top_k < 0 || top_k > 64 || top_k > m->c.vocab)) return MLLM_HIP_ERR_SHAPE;
-    if (method == 2 && !(top_p > 0.0f)) return MLLM_HIP_ERR_ARG;      // p <= 0 or NaN keeps no candidate at all (the reference then indexes an empty vector, Generate.cpp:116-118)
+    if (!m || !m->has_llm || m->cache_len <= 0 || steps <= 0) return MLLM_HIP_ERR_ARG;
+    EH(sampling_check(m, method, top_k, top_p, temperature, u01));
     if (m->cache_len + steps > m->c.cache_limit) { fprintf(stderr, "mllm_hip: KV cache overflow (%d + %d > %d)\n", m->cache_len, steps, m->c.cache_limit); return MLLM_HIP_ERR_SHAPE; }
     if (m->needs_arm) { EH(arm_decode(m)); m->needs_arm = false; }
     const int V = m->c.vocab;
@@ -1711,8 +1710,8 @@ extern "C" int mllm_hip_model_generate_sampled(mllm_hip_model *m, int32_t first_
         m->cache_len += 1;
         m->last_pos += 1.0f;
         int32_t next = 0;
-        if (method == 0 || (method == 1 && top_k <= 1)) {
-            // greedy: the device argmax of the step (std::max_element, first maximum); top-k with k in {0, 1} is the same (Generate.cpp:50-54)
+        if (sampling_is_argmax(method, top_k)) {
+            // the device argmax of the step (std::max_element, first maximum)
             HH(hipMemcpyAsync(&next, m->tok_dev, 4, hipMemcpyDeviceToHost, m->st));
             HH(hipStreamSynchronize(m->st));
         } else if (method == 1) {

@@ -139,6 +139,21 @@ def test_gemv_rows_15_and_first_gemm_rows_16():
     m.close()
 
 
+def test_gemv_rows_with_the_linear_head():
+    """TinyLlama (Linear Q4_K head), B = 4 with prompts of 3 and 5 ids: R = 14 rows, so every Linear of the pass takes the GEMV form and the Linear head runs over the four
+    gathered rows; three batch_decode steps on (B = 4: the step's packed GEMM)."""
+    from mllm_amd import lib
+    cfg, path = _setup("tinyllama")
+    turns = [((n, 300 + i),) for i, n in enumerate((3, 5, 3, 3))]
+    want = [_solo("tinyllama", t, 3) for t in turns]
+    m = lib.Model(cfg, path)
+    m.batch_begin(4)
+    nxt, lg, _ = m.batch_prefill([_ids("tinyllama", t[0]) for t in turns])
+    _check_prefill(nxt, lg, want)
+    _check_decode(m, nxt.tolist(), want, 3)
+    m.close()
+
+
 CASE3 = {"tinyllama": ("tlq", (6, 31), (11, 32)), "qwen15": ("qwen", (6, 33), (11, 34)), "heads8": ((40, 35), (6, 36), (33, 37))}
 TURN2 = ((3, 41), (9, 42), (33, 43))
 

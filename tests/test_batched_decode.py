@@ -159,3 +159,30 @@ def test_batched_rows_linear_head_b2_b3_on_the_full_range_file():
             assert np.array_equal(lg[i], want[b][1][pos[b]]), (s, b, float(np.abs(lg[i] - want[b][1][pos[b]]).max()))
             cur[b] = int(nxt[i])
     m.close()
+
+
+def test_batched_rows_linear_head_b4_takes_the_packed_gemm():
+    """TinyLlama (Q4_K, Linear head) on its full-range file with B = 4: from four rows on a batched step's Linears take the packed GEMM, and the Linear head runs over
+    four rows.  Prompts of 3 and 5 ids, three steps: every id and every logit equals the batch-1 runs."""
+    from mllm_amd import lib
+    cfg = synth.tinyllama_tiny(mf.Q4_K)
+    path = weights.causal_lm_file(cfg, CACHE, full_range=True)
+    r = np.random.default_rng(7)
+    prompts = [r.integers(0, cfg.vocab, size=n).astype(np.int32) for n in (3, 5, 5, 3)]
+    steps = 3
+    want = [_alone(lib, cfg, path, p, steps) for p in prompts]
+    m = lib.Model(cfg, path)
+    m.batch_begin(4)
+    cur = []
+    for b, p in enumerate(prompts):
+        m.batch_select(b)
+        tok, lg, _ = m.prefill(p)
+        assert tok == want[b][0][0] and np.array_equal(lg, want[b][1][0]), b
+        cur.append(tok)
+    for s in range(1, steps + 1):
+        nxt, lg, _ = m.batch_decode(cur)
+        for b in range(4):
+            assert int(nxt[b]) == want[b][0][s], (s, b)
+            assert np.array_equal(lg[b], want[b][1][s]), (s, b, float(np.abs(lg[b] - want[b][1][s]).max()))
+        cur = nxt.tolist()
+    m.close()
